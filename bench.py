@@ -469,6 +469,33 @@ def cpu_baseline_stream():
                        f"28 736 keys {t_ma:.2f}s, mask decoder heads {t_dec:.2f}s, memory encoder {t_me:.2f}s -> {total:.2f}s per frame; +-2x with host load")}
 
 
+# ------------------------------------------------------------------------------------------------ --dump-outputs
+DUMP_CAP = 1 << 20           # elements per written array: a larger output is written as a fixed, seeded sample of this many elements
+DUMP_BUDGET = 64 << 20       # bytes over all arrays of one run
+_dumped = [0]
+
+
+def _sample(t, cap=DUMP_CAP):
+    """`t` itself when it has at most `cap` elements, else the same `cap` (sorted) flat positions of it in every run."""
+    t = t.detach()
+    if t.numel() <= cap:
+        return t
+    idx = torch.randint(0, t.numel(), (cap,), generator=torch.Generator().manual_seed(0)).sort().values
+    return t.reshape(-1)[idx.to(t.device)]
+
+
+def dump_outputs(args, arrays, cap=DUMP_CAP):
+    """--dump-outputs DIR: {name: tensor} of the last timed step as DIR/<name>.npy, float32 (a tensor of more than `cap` elements sampled by _sample)."""
+    if not args.dump_outputs:
+        return
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    host = {k: _sample(v, cap).float().cpu().numpy() for k, v in arrays.items()}
+    _dumped[0] += sum(a.nbytes for a in host.values())
+    assert _dumped[0] <= DUMP_BUDGET, f"--dump-outputs: {_dumped[0]} bytes, over the {DUMP_BUDGET}-byte budget"
+    for k, a in host.items():
+        np.save(os.path.join(args.dump_outputs, k + ".npy"), a)
+
+
 # ------------------------------------------------------------------------------------------------ launcher
 def launch_ranks(args):
     """Parent of a multi-GPU run: never touches the GPU (torch.cuda.device_count() does not initialise it on this image), starts N ranks of this file
@@ -526,6 +553,7 @@ def ddp_selftest(args, rank, world):
         dist.all_gather(gs, g0)
         same = all(torch.equal(gs[0], t) for t in gs)
     if rank == 0:
+        dump_outputs(args, {"grad_param0": g0})
         print(json.dumps({"selftest": True, "metric": "ddp launcher self-test (toy module, CPU, gloo)", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                           "ms_per_step": round(float(el) / args.steps * 1e3, 3), "replicas_agree": bool(same), "buckets": len(reducer.buckets)}), flush=True)
     if world > 1:
@@ -585,6 +613,8 @@ def sam2_stream(args, dev, rank, world, dist):
             sess, res = step()
         barrier()
         elapsed = time.perf_counter() - t0
+        if rank == 0:
+            dump_outputs(args, {"stream_masks": torch.stack([m_ for _, m_ in res])})
         timed_only = bool(os.environ.get("RGA3_BENCH_TIMED_ONLY"))   # profiling runs: nothing after the timed stream (the variants below would end the trace)
         multi = None
         if NOBJ > 1 and not timed_only:   # the same objects one after the other on one stream, and ONE object: what tracking them together buys
@@ -808,6 +838,8 @@ def measure_forward(model_fwd, inputs, args, rank, refine=True):
         out = step()
     torch.cuda.synchronize()
     ms = (time.perf_counter() - t0) / args.steps * 1e3
+    if rank == 0:
+        dump_outputs(args, {"forward_logits": out.logits})
     if rank != 0 or os.environ.get("RGA3_BENCH_TIMED_ONLY"):   # (the env switch ends the process after the timed steps: rocprofv3 timeline captures)
         return ms, None, None
     # ---- same process, same board, interleaved: the two round-4 changes of this path switched off one at a time (boards differ by +-2 %: only an A/B inside
@@ -916,10 +948,14 @@ def main():
     ap.add_argument("--sam-prefetch-layer", type=int, default=7, help="training modes: the next sample's SAM2 encoder is launched when the backward reaches this decoder layer")
     ap.add_argument("--no-sam-prefetch", action="store_true", help="training modes: do not run the frozen SAM2 image encoder of the next sample beside the optimizer step (A/B)")
     ap.add_argument("--no-prefetch", action="store_true", help="training modes: do not run the frozen vision tower of the next sample one step ahead on a side stream (A/B)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32; a large "
+                                                             "output as a fixed, seeded sample; at most 64 MB in all): inputs are seeded, so two builds compare output for output")
     ap.add_argument("--batches", choices=["fresh", "repeat"], default="fresh",
                     help="training modes: fresh = a new sample (new tensor objects, new token ids, [SEG] position, pixel tensors from a resident pool of 4) every step, as a "
                          "training loop feeds it; repeat = the same tensor objects every step with the host plan reused (round 2's measurement)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return launch_ranks(args)
@@ -1023,7 +1059,7 @@ def main():
         sam_pf_param = next((p_ for p_ in lay.parameters() if p_.requires_grad), None)      # its LoRA factor: the gradient arrives when that layer's backward is done
     model.reuse_host_plan(args.batches == "repeat")
 
-    def step(sync=True):
+    def step(sync=True, keep=None):
         reducer.begin_step()
         for mi in range(accum):   # gradient accumulation: gradients are exchanged once per optimizer step (DDP no_sync)
             reducer.begin_micro_step()
@@ -1033,6 +1069,9 @@ def main():
                 model.prefetch_next(**feed.peek_pixels())
             out = model(**cur)
             loss = out["loss"] if isinstance(out, dict) else out.loss
+            if keep is not None:    # --dump-outputs: what this step hands its caller (the last micro-step's outputs)
+                items = out.items() if isinstance(out, dict) else (("loss", out.loss), ("logits", out.logits))
+                keep.update((k, v.detach()) for k, v in items if isinstance(v, torch.Tensor))
             if pf and not full:  # no mask path in this mode: behind the forward, beside the backward / optimizer
                 model.prefetch_vision(**feed.peek_pixels())
             if pf and sam_prefetch and full and mi + 1 == accum:
@@ -1060,15 +1099,20 @@ def main():
         step()
     barrier()
     del losses[:]
+    last = {} if args.dump_outputs else None
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
+    for i in range(args.steps):
+        step(keep=last if i == args.steps - 1 else None)
     barrier()
     elapsed = time.perf_counter() - t0
     if dist is not None:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if rank == 0 and last is not None:      # the step's outputs and the trainable weights its optimizer step left (before any untimed step below moves them)
+        dump_outputs(args, {"train_" + k: v for k, v in last.items()})
+        per = min(16384, (4 << 20) // len(trainables))
+        dump_outputs(args, {"train_trainable_params": torch.cat([_sample(p_, per).reshape(-1).float() for p_ in trainables])}, cap=4 << 20)
     lv = torch.stack([l.float().reshape(()) for l in losses]).cpu()
     assert torch.isfinite(lv).all(), "non-finite loss"
     if rank == 0 and os.environ.get("RGA3_BENCH_ATEN_CENSUS"):

@@ -6,6 +6,8 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -38,3 +40,24 @@ def test_more_gpus_than_visible_fails_loudly():
 def test_world_size_mismatch_is_an_error():
     r = _run("--gpus", "1", "--mode", "ddp_selftest", env={"WORLD_SIZE": "2", "RANK": "0", "LOCAL_RANK": "0"})
     assert r.returncode != 0 and "WORLD_SIZE=2" in r.stderr
+
+
+def test_dump_outputs_repeat_run_for_run(tmp_path):
+    # --dump-outputs writes the last timed step's outputs as float32 .npy; seeded inputs make two runs agree array for array
+    got = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        r = _run("--gpus", "1", "--mode", "ddp_selftest", "--steps", "4", "--warmup", "1", "--dump-outputs", str(d))
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert line["steps"] == 4 and line["ms_per_step"] > 0
+        got.append({f: np.load(d / f) for f in sorted(os.listdir(d))})
+    assert list(got[0]) == ["grad_param0.npy"]
+    a = got[0]["grad_param0.npy"]
+    assert a.dtype == np.float32 and a.shape == (256, 64) and np.isfinite(a).all() and np.abs(a).sum() > 0
+    assert np.array_equal(a, got[1]["grad_param0.npy"])
+
+
+def test_steps_below_one_is_an_error():
+    r = _run("--gpus", "1", "--mode", "ddp_selftest", "--steps", "0")
+    assert r.returncode != 0 and "--steps" in r.stderr
