@@ -6,11 +6,16 @@ BASELINE.json configs[2] per GPU — the complete RGA3 training micro-step of re
 synthetic sample per GPU: Qwen2.5-VL-7B ViT (frozen) + decoder forward/backward with LoRA r128 on q/v, lm_head and
 embed_tokens trainable, SAM2-L on 16 frames 1024x1024 (frozen Hiera-L + FPN, trainable mask decoder + text_hidden_fcs,
 BCE + dice), bucketed gradient exchange, AdamW.  A "step" is one such micro-step + optimizer step; `value` = samples/s
-over all ranks.  The same process also measures BASELINE.json configs[1] (ViT + LLM forward, S = 2112) on the same
-weights: that is the `roofline` object (dominant kernel family = the bf16 MFMA GEMM, HIP events on the launch stream
-around every GEMM launch; `whole_forward_frac` is the >= 40 % target of the north star); `roofline_fwd_bwd` is the
-same measurement for the timed training step.  `cpu_baseline` times the fp32 oracle restatement (a "port": the
-reference is Python and cannot travel) on the host cores on a bounded sample of the same fwd+bwd workload.
+over all ranks.  The same process first times BASELINE.json configs[1] (ViT + LLM forward, S = 2112) on the same weights
+(its in-situ tile refinement sets the tilings the training step then runs).
+
+A plain run does only what `value` needs: it sets up, warms up, times the steps, writes --dump-outputs and prints the line,
+whose `roofline` is then the whole-step algorithmic FLOPs / step time.  `--full` adds everything else, each part outside the
+timed steps: the configs[1] `roofline` object (dominant kernel family = the bf16 MFMA GEMM, HIP events on the launch stream
+around every GEMM launch; `whole_forward_frac` is the >= 40 % target of the north star) with its A/B variants, board sample
+and output check against the tile-10 kernel; `roofline_fwd_bwd.gemm_family`, the same measurement for the training step;
+the step variants; the exchange report of a multi-GPU run; and `cpu_baseline`, the fp32 oracle restatement (a "port": the
+reference is Python and cannot travel) on the host cores on a bounded sample of the same workload.
 
 `--gpus N` with N > 1 and no torchrun environment: this process launches N ranks of itself (one per GPU, RCCL) BEFORE
 touching the GPU and exits with their code; with fewer than N visible GPUs it exits non-zero.  Under the driver's
@@ -615,7 +620,8 @@ def sam2_stream(args, dev, rank, world, dist):
         elapsed = time.perf_counter() - t0
         if rank == 0:
             dump_outputs(args, {"stream_masks": torch.stack([m_ for _, m_ in res])})
-        timed_only = bool(os.environ.get("RGA3_BENCH_TIMED_ONLY"))   # profiling runs: nothing after the timed stream (the variants below would end the trace)
+        # a plain run, and profiling runs: nothing after the timed stream (the variants below would end the trace)
+        timed_only = bool(os.environ.get("RGA3_BENCH_TIMED_ONLY")) or not args.full
         multi = None
         if NOBJ > 1 and not timed_only:   # the same objects one after the other on one stream, and ONE object: what tracking them together buys
             def timed(**kw):
@@ -709,7 +715,8 @@ def sam2_stream(args, dev, rank, world, dist):
                 "config": {"workload": f"BASELINE.json configs[3]: SAM2-L (random init) memory path over {T} frames 1024x1024: frame 0 prompted with a language "
                                        "embedding, frames 1.. propagate (memory attention over <= 7 memory frames + <= 16 object pointers, mask decoder, "
                                        "memory encoder); image features precomputed outside the timed region", "frames": T, "parallelism": f"replicas x{world}",
-                           "prompt_every_frame_frames_per_s": round(world * T / (elapsed_prompt / args.steps), 2), "encoder_inclusive_frames_per_s": round(world * T / (elapsed_enc / args.steps), 2), "counts": sess.counts, "objects": NOBJ, "multi_object": multi},
+                           "prompt_every_frame_frames_per_s": None if timed_only else round(world * T / (elapsed_prompt / args.steps), 2),
+                           "encoder_inclusive_frames_per_s": None if timed_only else round(world * T / (elapsed_enc / args.steps), 2), "counts": sess.counts, "objects": NOBJ, "multi_object": multi},
                 "roofline": dom if dom is not None else {"bound": "mfma", "achieved": None, "peak": PEAK_BF16 / 1e12, "unit": "TFLOP/s", "frac": None, "traffic": None},
                 "roofline_stream": {"bound": "mfma", "achieved": round(fl / sec / 1e12, 1), "peak": PEAK_BF16 / 1e12, "unit": "TFLOP/s",
                                     "frac": round(fl / sec / PEAK_BF16, 4), "traffic": None,
@@ -817,6 +824,53 @@ def _board_sample(step, seconds=3.0):
 
 
 # ------------------------------------------------------------------------------------------------ main
+def _median_unless_above(step, reps, bar):
+    """tuner._time_step's median of `reps` timed steps, or inf as soon as that median can no longer fall below `bar`: with k of the reps known, the median
+    is at least their (reps // 2 - (reps - k))-th fastest, whatever the runs still to come give."""
+    ts = []
+    for k in range(1, reps + 1):
+        st, en = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        st.record()
+        step()
+        en.record()
+        en.synchronize()
+        ts.append(st.elapsed_time(en))
+        ts.sort()
+        lo = reps // 2 - (reps - k)
+        if k < reps and lo >= 0 and ts[lo] >= bar:
+            return float("inf")
+    return ts[reps // 2]
+
+
+def refine_tilings(step, reps=5, within=1.5, min_gain=0.002):
+    """tuner.refine with the same decision rule (a candidate tiling replaces the current one when the step's median of `reps` runs beats the best so far by
+    `min_gain`), but a candidate is dropped after the runs that already rule it out: a clearly slower tiling costs 3 runs of 5, not 5."""
+    from rga3.hip import tuner
+    if not tuner._enabled:
+        return {}
+    step()
+    torch.cuda.synchronize()
+    changed = {}
+    base = tuner._time_step(step, reps)
+    for key in list(tuner._cache):
+        tm = tuner._times.get(key)
+        if not tm:
+            continue
+        cur = tuner._cache[key]
+        lim = min(tm.values()) * within
+        best_t, best_ms = cur, base
+        for cand in sorted((t for t in tm if t != cur and tm[t] <= lim), key=lambda t: tm[t]):
+            tuner._cache[key] = cand
+            ms = _median_unless_above(step, reps, best_ms * (1.0 - min_gain))
+            if ms < best_ms * (1.0 - min_gain):
+                best_t, best_ms = cand, ms
+        tuner._cache[key] = best_t
+        if best_t != cur:
+            changed[key] = (cur, best_t)
+            base = best_ms
+    return changed
+
+
 def measure_forward(model_fwd, inputs, args, rank, refine=True):
     """configs[1]: K timed forwards (+ the GEMM-family instrumented pass and the output check on rank 0).  Returns (ms per step, roofline dict, verify dict)."""
     from rga3.hip import ops, tuner
@@ -827,7 +881,7 @@ def measure_forward(model_fwd, inputs, args, rank, refine=True):
 
     if refine and not args.no_refine:
         rw, rr = (os.environ.get("RGA3_REFINE", "1.5,5").split(",") + ["5"])[:2]
-        ch = tuner.refine(step, reps=int(rr), within=float(rw))
+        ch = refine_tilings(step, reps=int(rr), within=float(rw))
         if rank == 0 and ch:
             print("tuner.refine changed %d shape(s): %s" % (len(ch), {str(k[:3]): v for k, v in ch.items()}), file=sys.stderr)
     for _ in range(args.warmup):
@@ -841,6 +895,9 @@ def measure_forward(model_fwd, inputs, args, rank, refine=True):
     if rank == 0:
         dump_outputs(args, {"forward_logits": out.logits})
     if rank != 0 or os.environ.get("RGA3_BENCH_TIMED_ONLY"):   # (the env switch ends the process after the timed steps: rocprofv3 timeline captures)
+        return ms, None, None
+    if not args.full:       # a plain run: the roofline, variants and output check below are --full only
+        assert ops.gemm_stream_k_timeouts() == 0, "stream-K hand-off timed out: results of this run are not trustworthy"
         return ms, None, None
     # ---- same process, same board, interleaved: the two round-4 changes of this path switched off one at a time (boards differ by +-2 %: only an A/B inside
     #      one process prices a 1 - 2 % change).  Tilings stay as decided above; the unfolded route launches the same product shapes.
@@ -927,10 +984,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-board", action="store_true", help="skip the board power / shader clock sample (roofline.board)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond `value`, after the timed steps: CPU baseline, configs[1] forward roofline with its variants, "
+                         "board sample and tile-10 output check, the training step's GEMM-family pass and variants, the multi-GPU exchange report, the "
+                         "sam2_stream variants and dominant-kernel pass.  Off: set up, warm up, time the steps, --dump-outputs, print the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-board", action="store_true", help="--full without the board power / shader clock sample (roofline.board)")
     ap.add_argument("--mode", choices=["headline", "forward", "train", "train_full", "sam2_stream", "lora_fp8", "ddp_selftest"], default="headline",
-                    help="headline (default) = BASELINE metric: configs[2] per GPU, full RGA3 (Qwen2.5-VL-7B + SAM2-L, 16 SAM frames) fwd+bwd + AdamW as `value`, plus the "
+                    help="headline (default) = BASELINE metric: configs[2] per GPU, full RGA3 (Qwen2.5-VL-7B + SAM2-L, 16 SAM frames) fwd+bwd + AdamW as `value`, plus (--full) the "
                          "configs[1] forward roofline in the same line; forward = configs[1] only; train = LLM-side LoRA step without SAM2; train_full = headline without "
                          "the forward leg; lora_fp8 = configs[4]: LoRA step, 32 frames 448x448 (S = 4160), grad-accum 4, e4m3 GEMMs for the frozen decoder weights; "
                          "sam2_stream = configs[3]: SAM2-L memory-attention mask-decoder stream over 32 frames 1024x1024, prompt on frame 0; "
@@ -1023,7 +1084,11 @@ def main():
                 dist.all_reduce(t, op=dist.ReduceOp.MAX)
             ms = float(t.item())
             if rank == 0:
-                cpu = None if (args.no_cpu_baseline or world > 1) else cpu_baseline(train=False)
+                cpu = None if (not args.full or args.no_cpu_baseline or world > 1) else cpu_baseline(train=False)
+                if fwd_roof is None:    # a plain run: whole-forward algorithmic FLOPs / forward time (no run of its own)
+                    fwd_roof = {"bound": "mfma", "achieved": round(TOTAL_FLOPS / (ms * 1e-3) / 1e12, 1), "peak": PEAK_BF16 / 1e12, "unit": "TFLOP/s",
+                                "frac": round(TOTAL_FLOPS / (ms * 1e-3) / PEAK_BF16, 4), "traffic": None, "flops_per_forward": TOTAL_FLOPS,
+                                "note": "whole-forward algorithmic FLOPs / forward time; the GEMM-family figures need --full"}
                 line = {"metric": "video-QA samples/sec at 7B/16-frame (configs[1]: visual-encoder+LLM forward)", "value": round(world * 1e3 / ms, 4),
                         "unit": "samples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 3),
                         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
@@ -1093,8 +1158,7 @@ def main():
         return loss
 
     if args.refine and world == 1:
-        from rga3.hip import tuner
-        tuner.refine(step, reps=3, within=1.5)
+        refine_tilings(step, reps=3, within=1.5)
     for _ in range(args.warmup):
         step()
     barrier()
@@ -1147,7 +1211,7 @@ def main():
 
     # ---- communication report (N > 1): step time without the exchange, stand-alone bus bandwidth of the buckets
     comm = None
-    if world > 1:
+    if world > 1 and args.full:
         barrier()
         t0 = time.perf_counter()
         for _ in range(max(3, args.steps // 2)):
@@ -1183,7 +1247,8 @@ def main():
                 "step_ms_without_exchange": round(local_ms, 3), "exposed_comm_ms": round(ms - local_ms, 3),
                 "xgmi_peak_GB_per_s_per_gpu": 7 * 153}
 
-    timed_only = bool(os.environ.get("RGA3_BENCH_TIMED_ONLY"))   # profiling runs: nothing after the timed steps (the instrumented pass and the variants would end the trace)
+    # a plain run, and profiling runs: nothing after the timed steps (the instrumented pass and the variants would end the trace)
+    timed_only = bool(os.environ.get("RGA3_BENCH_TIMED_ONLY")) or not args.full
     # ---- GEMM-family instrumented pass over the same step (rank 0)
     roof_tr = None
     if rank == 0 and world == 1 and not timed_only:
@@ -1261,7 +1326,7 @@ def main():
                 "roofline": {"bound": "mfma", "achieved": round(fl / (ms * 1e-3) / 1e12, 1), "peak": peak / 1e12, "unit": "TFLOP/s", "frac": round(fl / (ms * 1e-3) / peak, 4),
                              "traffic": None, "gemm_family": roof_tr, "note": "whole-step algorithmic FLOPs / step time against the dense fp8 (5 PF) or bf16 (2.5 PF) MFMA peak"},
                 "loss_first_last": [round(float(lv[0]), 5), round(float(lv[-1]), 5)], "comm": comm,
-                "cpu_baseline": None if (args.no_cpu_baseline or world > 1) else cpu_baseline(train=True, sam_frames=0, seq=4160, grid_t=16, micro_steps=accum)}
+                "cpu_baseline": None if (not args.full or args.no_cpu_baseline or world > 1) else cpu_baseline(train=True, sam_frames=0, seq=4160, grid_t=16, micro_steps=accum)}
         _put_traffic(line["roofline"], "lora_fp8", "gemm")
         print(json.dumps(line), flush=True)
     elif rank == 0:
@@ -1270,7 +1335,7 @@ def main():
                "traffic": None, "flops_per_step": fl, "gemm_family": roof_tr, "note": "whole-step algorithmic FLOPs (SURVEY.md 8(d); activations kept, nothing recomputed) / step time"}
         _put_traffic(rfb, "train_full")
         cpu = None
-        if full and world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and args.full and not args.no_cpu_baseline:
             cpu = cpu_baseline(train=True, sam_frames=args.sam_frames)
         line = {"metric": ("video-QA samples/sec (fwd+bwd) at 7B/16-frame — full RGA3 training step (Qwen2.5-VL-7B + SAM2-L + mask losses + AdamW)" if full
                            else "video-QA samples/sec (fwd+bwd) at 7B/16-frame — LLM-side LoRA training step (no SAM2 mask path)"), "value": round(value, 4),

@@ -269,3 +269,58 @@ def test_stom_closing_against_an_independent_library():
         ys, xs = np.nonzero(got)
         cy, cx = ndimage.center_of_mass(got)
         assert abs(cy - ys.mean()) < 1e-9 and abs(cx - xs.mean()) < 1e-9      # cv2.moments m01 / m00, m10 / m00 of a 0 / 255 image = the mean coordinates
+
+
+def test_bench_refine_decides_as_tuner_refine(monkeypatch):
+    """bench.refine_tilings drops a candidate tiling as soon as its median of `reps` step times can no longer beat the best so far; on the same step times it
+    reaches tuner.refine's decisions, in fewer steps."""
+    import importlib
+    import zlib
+
+    bench = importlib.import_module("bench")
+    from rga3.hip import tuner
+
+    clock, runs, seen = [0.0], [0], {}
+
+    class Ev:
+        def __init__(self, enable_timing=False):
+            self.t = None
+
+        def record(self):
+            self.t = clock[0]
+
+        def synchronize(self):
+            pass
+
+        def elapsed_time(self, other):
+            return other.t - self.t
+
+    monkeypatch.setattr(torch.cuda, "Event", Ev)
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda *a, **k: None)
+    monkeypatch.setattr(tuner, "_enabled", True)
+    rng = np.random.default_rng(0)
+    tiles = (20, 22, 27, 31, 5, 12)
+    keys = [(9, n, 3584, "none", False, False, False) for n in (512, 3584, 18944, 37888)]
+    cost = {k: {t: float(rng.uniform(1.0, 1.7)) for t in tiles} for k in keys}
+    alone = {k: {t: c * float(rng.uniform(0.8, 1.2)) for t, c in cost[k].items()} for k in keys}     # stand-alone times: not the order in place
+
+    def step():
+        # the n-th run of one choice of tilings always takes the same time: both refines see the same samples of every choice they time
+        state = tuple(tuner._cache[k] for k in keys)
+        n = seen[state] = seen.get(state, -1) + 1
+        clock[0] += sum(cost[k][t] for k, t in zip(keys, state)) + (zlib.crc32(repr((state, n)).encode()) % 1000) * 2e-4
+        runs[0] += 1
+
+    def run(fn, **kw):
+        monkeypatch.setattr(tuner, "_cache", {k: min(tiles, key=lambda t: alone[k][t]) for k in keys})
+        monkeypatch.setattr(tuner, "_times", {k: dict(alone[k]) for k in keys})
+        seen.clear()
+        runs[0] = 0
+        changed = fn(step, **kw)
+        return changed, dict(tuner._cache), runs[0]
+
+    for reps, within in ((5, 1.5), (3, 1.5), (5, 1.2)):
+        ch_ref, cache_ref, n_ref = run(tuner.refine, reps=reps, within=within)
+        ch, cache, n = run(bench.refine_tilings, reps=reps, within=within)
+        assert ch == ch_ref and cache == cache_ref, (reps, within)
+        assert ch_ref and n < n_ref, (reps, within, n, n_ref)

@@ -2,7 +2,7 @@
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out; mkdir -p $O
 cd $R && timeout 1500 python3 -m pytest tests/ -x -q -m gpu > $O/r03_gpu_tests.log 2>&1; tail -4 $O/r03_gpu_tests.log
 cd /tmp && export TMPDIR=/tmp
-B="python3 $R/bench.py"
+B="python3 $R/bench.py --full"
 timeout 600 $B --steps 10 --warmup 3 --no-cpu-baseline > $O/r03_headline_mlp.json 2> $O/r03_headline_mlp.err; python3 -c "
 import json;d=json.loads(open('$O/r03_headline_mlp.json').read().strip().splitlines()[-1]);print('HEADLINE',d['value'],d['ms_per_step'],d['roofline']['forward_ms_per_step'],d['config']['variants'])"
 export RGA3_BENCH_TIMED_ONLY=1

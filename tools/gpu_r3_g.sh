@@ -2,7 +2,7 @@
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out; mkdir -p $O
 cd $R && timeout 600 python3 -m pytest tests/test_sam2_kernels_gpu.py tests/test_train_gpu.py -x -q -m gpu > $O/r03_g_tests.log 2>&1; tail -3 $O/r03_g_tests.log
 cd /tmp && export TMPDIR=/tmp
-B="python3 $R/bench.py"
+B="python3 $R/bench.py --full"
 timeout 900 $B --steps 20 --warmup 5 --no-cpu-baseline > $O/r03_headline_final_a.json 2> $O/r03_headline_final_a.err; python3 -c "
 import json;d=json.loads(open('$O/r03_headline_final_a.json').read().strip().splitlines()[-1]);print('HEADLINE',d['value'],d['ms_per_step'],d['roofline']['forward_ms_per_step'],d['roofline']['whole_forward_frac'],d['config']['variants'])"
 export RGA3_BENCH_TIMED_ONLY=1

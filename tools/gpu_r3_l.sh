@@ -5,7 +5,7 @@ timeout 900 python -m pytest tests/test_sam2_kernels_gpu.py -x -q -k "memory_lay
 timeout 900 python -m pytest tests/test_sam2_gpu.py tests/test_fullsize_parity_gpu.py -x -q -k "memory or stream or session or propagat or video" 2>&1 | tail -3
 for i in 1 2; do
 for f in "" "--no-rowchain"; do
-timeout 600 python bench.py --mode sam2_stream $f --steps 5 --warmup 2 2>&1 | F="$f" python3 -c "
+timeout 600 python bench.py --full --mode sam2_stream $f --steps 5 --warmup 2 2>&1 | F="$f" python3 -c "
 import sys, json, os
 ok = False
 for l in sys.stdin:

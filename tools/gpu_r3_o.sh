@@ -2,7 +2,7 @@
 # configs[4] (lora_fp8): PMC traffic passes once more, with everything that has tripped the profiler switched off (fresh pinned uploads, the side-stream vision prefetch)
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out; mkdir -p $O
-B="python3 $R/bench.py"
+B="python3 $R/bench.py --full"
 export RGA3_BENCH_TIMED_ONLY=1
 for try in 1 2; do
 rm -rf /tmp/f8f

@@ -14,4 +14,4 @@ for set in "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES GRBM_GUI_ACTI
   echo "pass $i ($set) rc $?"
 done
 python3 $R/tools/pmc_pipe_util.py sum /tmp/pu $O/r04a_pmc_pipe_util.json 2>&1 | tail -80
-python3 $R/bench.py --mode forward --steps 20 --warmup 5 --no-cpu-baseline > $O/r04a_bench_forward.json 2> $O/r04a_bench_forward.err; tail -c 1500 $O/r04a_bench_forward.json
+python3 $R/bench.py --full --mode forward --steps 20 --warmup 5 --no-cpu-baseline > $O/r04a_bench_forward.json 2> $O/r04a_bench_forward.err; tail -c 1500 $O/r04a_bench_forward.json

@@ -6,7 +6,7 @@ cd $R
 MODE=${1:-forward}
 for rep in 1 2; do
  for v in old -; do
-  timeout -k 10 600 python3 tools/probes/bench_with_lib.py $v --mode $MODE --steps 20 --warmup 5 --no-cpu-baseline > $O/ab_${v}_$rep.json 2> $O/ab_${v}_$rep.err
+  timeout -k 10 600 python3 tools/probes/bench_with_lib.py $v --full --mode $MODE --steps 20 --warmup 5 --no-cpu-baseline > $O/ab_${v}_$rep.json 2> $O/ab_${v}_$rep.err
   python3 - $O/ab_${v}_$rep.json $v <<'P'
 import json,sys
 try:

@@ -5,7 +5,7 @@ O=$R/gpurun_out
 cd /tmp && export TMPDIR=/tmp
 for m in on off; do
   if [ $m = off ]; then export RGA3_RMS_FOLD=0; else export RGA3_RMS_FOLD=1; fi
-  rm -rf /tmp/pf_$m; timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pf_$m -o fwd -- python3 $R/bench.py --mode forward --steps 20 --warmup 3 --no-cpu-baseline > $O/r04d_prof_$m.log 2>&1
+  rm -rf /tmp/pf_$m; timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pf_$m -o fwd -- python3 $R/bench.py --full --mode forward --steps 20 --warmup 3 --no-cpu-baseline > $O/r04d_prof_$m.log 2>&1
   cp $(find /tmp/pf_$m -name "*kernel_stats.csv" | head -1) $O/r04d_fwd_kernel_stats_$m.csv
 done
 python3 - <<'P'

@@ -4,9 +4,9 @@ O=$R/gpurun_out
 cd /tmp && export TMPDIR=/tmp
 for m in on off; do
   if [ $m = off ]; then export RGA3_RMS_FOLD=0; else export RGA3_RMS_FOLD=1; fi
-  RGA3_TUNE_SAVE=$O/r04f_tuner_$m.json python3 $R/bench.py --mode forward --steps 10 --warmup 3 --no-cpu-baseline > $O/r04f_fwd_$m.json 2> $O/r04f_fwd_$m.err
+  RGA3_TUNE_SAVE=$O/r04f_tuner_$m.json python3 $R/bench.py --full --mode forward --steps 10 --warmup 3 --no-cpu-baseline > $O/r04f_fwd_$m.json 2> $O/r04f_fwd_$m.err
   export RGA3_TUNE_LOAD=$O/r04f_tuner_$m.json RGA3_BENCH_TIMED_ONLY=1
-  rm -rf /tmp/pf_$m; timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pf_$m -o fwd -- python3 $R/bench.py --mode forward --steps 20 --warmup 3 --no-refine --no-cpu-baseline > $O/r04f_prof_$m.log 2>&1
+  rm -rf /tmp/pf_$m; timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pf_$m -o fwd -- python3 $R/bench.py --full --mode forward --steps 20 --warmup 3 --no-refine --no-cpu-baseline > $O/r04f_prof_$m.log 2>&1
   cp $(find /tmp/pf_$m -name "*kernel_stats.csv" | head -1) $O/r04f_fwd_kernel_stats_$m.csv
   unset RGA3_TUNE_LOAD RGA3_BENCH_TIMED_ONLY
 done

@@ -3,7 +3,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/fp
-timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/fp -- python3 $R/bench.py --mode forward --steps 10 --warmup 3 --no-refine --no-cpu-baseline > $O/r04j_fwdprof.log 2>&1
+timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/fp -- python3 $R/bench.py --full --mode forward --steps 10 --warmup 3 --no-refine --no-cpu-baseline > $O/r04j_fwdprof.log 2>&1
 f=$(find /tmp/fp -name '*kernel_stats.csv' | head -1); cp $f $O/r04j_fwd_kernel_stats.csv
 python3 - $O/r04j_fwd_kernel_stats.csv <<'P'
 import csv, sys

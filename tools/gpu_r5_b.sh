@@ -7,7 +7,7 @@ cd $R
 timeout -k 10 1500 python3 -m pytest -x -q -s -m gpu tests/test_fulldepth_parity_gpu.py > $O/r05b_fulldepth.log 2>&1; echo "fulldepth rc $?"; grep -E "FULL_DEPTH_7B|FP8_LAYER|passed|failed|Error|assert" $O/r05b_fulldepth.log | cut -c1-1800 | tail -12
 timeout -k 10 900 python3 -m pytest -x -q -m gpu tests/test_sam2_gpu.py > $O/r05b_sam2.log 2>&1; echo "sam2 rc $?"; tail -15 $O/r05b_sam2.log | cut -c1-600
 for n in 1 2 4; do
-timeout -k 10 900 python3 bench.py --mode sam2_stream --objects $n --steps 5 --warmup 2 --no-cpu-baseline > $O/r05b_stream_$n.json 2> $O/r05b_stream_$n.err; echo "stream $n rc $?"
+timeout -k 10 900 python3 bench.py --full --mode sam2_stream --objects $n --steps 5 --warmup 2 --no-cpu-baseline > $O/r05b_stream_$n.json 2> $O/r05b_stream_$n.err; echo "stream $n rc $?"
 python3 - $O/r05b_stream_$n.json <<'P'
 import json,sys
 try:

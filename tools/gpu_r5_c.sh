@@ -10,7 +10,7 @@ timeout -k 10 900 python3 -m pytest -x -q -m gpu tests/test_sam2_gpu.py tests/te
 timeout -k 10 900 python3 -m pytest -x -q -s -m gpu tests/test_fulldepth_parity_gpu.py -k fp8 > $O/r05c_fp8layer.log 2>&1; echo "fp8 layer rc $?"; grep -E "FP8_LAYER|passed|failed" $O/r05c_fp8layer.log | cut -c1-1500
 timeout -k 10 600 python3 -m pytest -x -q -m gpu tests/test_train_gpu.py -k "lora_fold" > $O/r05c_lora.log 2>&1; echo "lora rc $?"; tail -3 $O/r05c_lora.log | cut -c1-800
 for n in 1 2 4; do
-timeout -k 10 900 python3 bench.py --mode sam2_stream --objects $n --steps 5 --warmup 2 --no-cpu-baseline > $O/r05c_stream_$n.json 2> $O/r05c_stream_$n.err; echo "stream $n rc $?"
+timeout -k 10 900 python3 bench.py --full --mode sam2_stream --objects $n --steps 5 --warmup 2 --no-cpu-baseline > $O/r05c_stream_$n.json 2> $O/r05c_stream_$n.err; echo "stream $n rc $?"
 python3 - $O/r05c_stream_$n.json <<'P'
 import json,sys
 try:
@@ -18,7 +18,7 @@ try:
 except Exception as e: print('parse', e)
 P
 done
-timeout -k 10 900 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/r05c_headline.json 2> $O/r05c_headline.err; echo "headline rc $?"
+timeout -k 10 900 python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/r05c_headline.json 2> $O/r05c_headline.err; echo "headline rc $?"
 python3 - $O/r05c_headline.json <<'P'
 import json,sys
 try:

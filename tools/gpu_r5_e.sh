@@ -8,7 +8,7 @@ timeout -k 10 600 python3 tools/probes/hm_ablate.py > $O/r05e_hm_ablate.log 2>&1
 for MODE in forward train_full; do
 for rep in 1 2; do
  for v in old -; do
-  timeout -k 10 600 python3 tools/probes/bench_with_lib.py $v --mode $MODE --steps 20 --warmup 5 --no-cpu-baseline > $O/r05e_ab_${MODE}_${v}_$rep.json 2> $O/r05e_ab_${MODE}_${v}_$rep.err
+  timeout -k 10 600 python3 tools/probes/bench_with_lib.py $v --full --mode $MODE --steps 20 --warmup 5 --no-cpu-baseline > $O/r05e_ab_${MODE}_${v}_$rep.json 2> $O/r05e_ab_${MODE}_${v}_$rep.err
   python3 - $O/r05e_ab_${MODE}_${v}_$rep.json $v $MODE <<'P'
 import json,sys
 try:

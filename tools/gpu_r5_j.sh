@@ -6,7 +6,7 @@ timeout -k 10 600 python3 -m pytest -x -q -m gpu tests/test_kernels_gpu.py -k "l
 for v in oldattn -; do echo "lib $v:"; timeout -k 10 300 python3 tools/probes/run_with_lib.py $v tools/probes/ln_stats_probe.py 2>&1 | grep rows; done
 timeout -k 10 900 python3 -m pytest -x -q -m gpu tests/test_fullsize_parity_gpu.py -k "hiera" 2>&1 | tail -2
 for rep in 1 2; do for v in oldattn -; do
-  timeout -k 10 600 python3 tools/probes/bench_with_lib.py $v --mode train_full --steps 20 --warmup 5 --no-cpu-baseline > $O/r05j_ab_${v}_$rep.json 2> $O/r05j_ab_${v}_$rep.err
+  timeout -k 10 600 python3 tools/probes/bench_with_lib.py $v --full --mode train_full --steps 20 --warmup 5 --no-cpu-baseline > $O/r05j_ab_${v}_$rep.json 2> $O/r05j_ab_${v}_$rep.err
   python3 - $O/r05j_ab_${v}_$rep.json $v <<'P'
 import json,sys
 try:

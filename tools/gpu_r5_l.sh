@@ -5,7 +5,7 @@ O=$R/gpurun_out
 cd $R
 timeout -k 10 900 python3 -m pytest -x -q -m gpu tests/test_unigr_gpu.py -k prefetch > $O/r05l_unigr.log 2>&1; echo "unigr rc $?"; tail -3 $O/r05l_unigr.log | cut -c1-600
 for L in 0 4 7 10 14; do
-timeout -k 10 900 python3 bench.py --mode train_full --steps 20 --warmup 5 --no-cpu-baseline --sam-prefetch-layer $L > $O/r05l_train_$L.json 2> $O/r05l_train_$L.err
+timeout -k 10 900 python3 bench.py --full --mode train_full --steps 20 --warmup 5 --no-cpu-baseline --sam-prefetch-layer $L > $O/r05l_train_$L.json 2> $O/r05l_train_$L.err
 python3 - $O/r05l_train_$L.json $L <<'P'
 import json,sys
 try:

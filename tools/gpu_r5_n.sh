@@ -4,7 +4,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-B="python3 $R/bench.py"
+B="python3 $R/bench.py --full"
 $B --gpus 1 --steps 20 --warmup 5 > $O/r05n_bench_headline.json 2> $O/r05n_bench_headline.err; tail -c 300 $O/r05n_bench_headline.json
 rm -rf /tmp/p1; timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p1 -o head -- $B --steps 20 --warmup 5 --no-cpu-baseline > $O/r05n_prof_headline.log 2>&1
 cp $(find /tmp/p1 -name "*kernel_stats.csv" | head -1) $O/r05n_bench_headline_kernel_stats.csv

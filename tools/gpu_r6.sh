@@ -3,8 +3,8 @@
 #   newtests   the tests added this round (fast)
 #   encprof    SAM2-L image encoder alone, 16 frames: wall time + rocprofv3 kernel stats
 #   suite      the driver's two commands (pytest -m gpu, smoke)
-#   headline   python bench.py --gpus 1   (driver's command)
-#   forward    python bench.py --mode forward
+#   headline   python bench.py --full --gpus 1   (the default mode with everything it measures beside its headline)
+#   forward    python bench.py --full --mode forward
 #   stream     configs[3], 1 and 4 objects
 #   fp8        configs[4]
 #   fp8prof    rocprofv3 kernel statistics of one configs[4] optimizer step
@@ -40,27 +40,27 @@ for s in "$@"; do
       timeout -k 10 3000 python3 -m pytest tests/ -x -q -m gpu > $O/r06_gpu_tests.log 2>&1; echo "suite rc $?"; tail -3 $O/r06_gpu_tests.log | cut -c1-300
       timeout -k 10 600 python3 -c "import __graft_entry__ as g; g.smoke()" > $O/r06_smoke.log 2>&1; echo "smoke rc $?"; tail -2 $O/r06_smoke.log ;;
     headline)
-      python3 bench.py --gpus 1 > $O/r06_bench_headline.json 2> $O/r06_bench_headline.err; tail -c 400 $O/r06_bench_headline.json ;;
+      python3 bench.py --full --gpus 1 > $O/r06_bench_headline.json 2> $O/r06_bench_headline.err; tail -c 400 $O/r06_bench_headline.json ;;
     forward)
-      python3 bench.py --mode forward > $O/r06_bench_forward.json 2> $O/r06_bench_forward.err; tail -c 400 $O/r06_bench_forward.json ;;
+      python3 bench.py --full --mode forward > $O/r06_bench_forward.json 2> $O/r06_bench_forward.err; tail -c 400 $O/r06_bench_forward.json ;;
     stream)
-      python3 bench.py --mode sam2_stream --steps 5 --warmup 2 > $O/r06_bench_sam2_stream.json 2> $O/r06_bench_sam2_stream.err; tail -c 300 $O/r06_bench_sam2_stream.json
-      python3 bench.py --mode sam2_stream --objects 4 --steps 5 --warmup 2 --no-cpu-baseline > $O/r06_bench_sam2_stream_4obj.json 2> $O/r06_bench_sam2_stream_4obj.err; tail -c 300 $O/r06_bench_sam2_stream_4obj.json ;;
+      python3 bench.py --full --mode sam2_stream --steps 5 --warmup 2 > $O/r06_bench_sam2_stream.json 2> $O/r06_bench_sam2_stream.err; tail -c 300 $O/r06_bench_sam2_stream.json
+      python3 bench.py --full --mode sam2_stream --objects 4 --steps 5 --warmup 2 --no-cpu-baseline > $O/r06_bench_sam2_stream_4obj.json 2> $O/r06_bench_sam2_stream_4obj.err; tail -c 300 $O/r06_bench_sam2_stream_4obj.json ;;
     fp8)
-      python3 bench.py --mode lora_fp8 --steps 3 --warmup 1 > $O/r06_bench_lora_fp8.json 2> $O/r06_bench_lora_fp8.err; tail -c 300 $O/r06_bench_lora_fp8.json ;;
+      python3 bench.py --full --mode lora_fp8 --steps 3 --warmup 1 > $O/r06_bench_lora_fp8.json 2> $O/r06_bench_lora_fp8.err; tail -c 300 $O/r06_bench_lora_fp8.json ;;
     frameline)
-      rm -rf /tmp/pfs; (cd /tmp && timeout -k 10 900 rocprofv3 --kernel-trace --output-format csv -d /tmp/pfs -o st -- python3 $R/bench.py --mode sam2_stream --steps 2 --warmup 1 --no-cpu-baseline --no-board > $O/r06_prof_stream.log 2>&1)
+      rm -rf /tmp/pfs; (cd /tmp && timeout -k 10 900 rocprofv3 --kernel-trace --output-format csv -d /tmp/pfs -o st -- python3 $R/bench.py --full --mode sam2_stream --steps 2 --warmup 1 --no-cpu-baseline --no-board > $O/r06_prof_stream.log 2>&1)
       python3 tools/frame_timeline.py /tmp/pfs --list --anchor "${ANCHOR:-sam_select_kernel}" --group-ms 0.3 --frame ${FRAME:-50} > $O/r06_stream_frame_timeline.txt 2>&1; head -150 $O/r06_stream_frame_timeline.txt | cut -c1-150
       cut -d, -f8- $(find /tmp/pfs -name '*kernel_trace.csv' | head -1) | grep -o 'rga3::[a-z_0-9]*' | sort | uniq -c | sort -rn | head -50
       rm -rf /tmp/pfs ;;
     atencensus)
-      RGA3_BENCH_ATEN_CENSUS=$O/r06_train_step_aten_census.txt python3 bench.py --mode train_full --steps 3 --warmup 3 --no-cpu-baseline --no-board > /dev/null 2> $O/r06_atencensus.err; cat $O/r06_train_step_aten_census.txt | cut -c1-230 ;;
+      RGA3_BENCH_ATEN_CENSUS=$O/r06_train_step_aten_census.txt python3 bench.py --full --mode train_full --steps 3 --warmup 3 --no-cpu-baseline --no-board > /dev/null 2> $O/r06_atencensus.err; cat $O/r06_train_step_aten_census.txt | cut -c1-230 ;;
     fp8prof)
-      rm -rf /tmp/p8; (cd /tmp && timeout -k 10 1200 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p8 -o f8 -- python3 $R/bench.py --mode lora_fp8 --steps 1 --warmup 1 --no-cpu-baseline --no-board > $O/r06_prof_lora_fp8.log 2>&1)
+      rm -rf /tmp/p8; (cd /tmp && timeout -k 10 1200 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p8 -o f8 -- python3 $R/bench.py --full --mode lora_fp8 --steps 1 --warmup 1 --no-cpu-baseline --no-board > $O/r06_prof_lora_fp8.log 2>&1)
       f=$(find /tmp/p8 -name '*kernel_stats.csv' | head -1); [ -n "$f" ] && cp $f $O/r06_bench_lora_fp8_kernel_stats.csv && head -45 $O/r06_bench_lora_fp8_kernel_stats.csv | cut -c1-220
       rm -rf /tmp/p8 ;;
     timeline)
-      rm -rf /tmp/pt; timeout -k 10 1200 rocprofv3 --kernel-trace --output-format csv -d /tmp/pt -o tr -- python3 bench.py --mode train_full --steps 4 --warmup 3 --no-cpu-baseline --no-board > $O/r06_timeline_run.log 2>&1
+      rm -rf /tmp/pt; timeout -k 10 1200 rocprofv3 --kernel-trace --output-format csv -d /tmp/pt -o tr -- python3 bench.py --full --mode train_full --steps 4 --warmup 3 --no-cpu-baseline --no-board > $O/r06_timeline_run.log 2>&1
       python3 tools/step_timeline.py /tmp/pt --bin-ms 5 --from-ms 0 --to-ms 1000 --exclude gemm_ > $O/r06_train_step_timeline.txt 2>&1; head -70 $O/r06_train_step_timeline.txt | cut -c1-160
       rm -rf /tmp/pt ;;
     probe:*)

@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-B="python3 $R/bench.py"
+B="python3 $R/bench.py --full"
 # 1. the driver's command (default mode = BASELINE metric) and its kernel statistics
 $B --gpus 1 --steps 20 --warmup 5 > $O/r02_bench_headline.json 2> $O/r02_bench_headline.err; tail -c 400 $O/r02_bench_headline.json
 rm -rf /tmp/p1; rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p1 -o head -- $B --steps 20 --warmup 5 --no-cpu-baseline > $O/r02_prof_headline.log 2>&1

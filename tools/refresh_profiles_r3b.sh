@@ -4,7 +4,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-B="python3 $R/bench.py"
+B="python3 $R/bench.py --full"
 T="timeout -k 10"
 # 4. configs[3] stream: kernel statistics, one-frame timeline, PMC traffic of the memory cross-attention kernel (eager launches: counters and graph replay do not mix), the line
 export RGA3_BENCH_TIMED_ONLY=1
