@@ -36,6 +36,16 @@ def shifted_seg_mask(ids, seg_idx):
     return torch.cat([m[:, 1:], torch.zeros_like(m)[:, 0].unsqueeze(1)], dim=1)
 
 
+def _vision(batch):
+    """The pixel inputs of a batch as Q.forward takes them: images (pixel_values / image_grid_thw) and videos (pixel_values_videos / video_grid_thw), each
+    passed when present (reference :193-195, 349-351 hand both to the Qwen forward)."""
+    out = {}
+    for px, grid in (("pixel_values", "image_grid_thw"), ("pixel_values_videos", "video_grid_thw")):
+        if batch.get(px) is not None:
+            out[px], out[grid] = batch[px].float(), batch[grid]
+    return out
+
+
 def model_forward(P, PS, qcfg, scfg, batch, weights, seg_token_idx, out_dim=256, inference=False, internals=None):
     """reference :149-321.  P: Qwen+head params, PS: SAM2 params (names without the 'grounding_encoder.sam2_model.' prefix).
     weights = (ce, dice, bce).  inference=True is the branch validate() drives (reference :236-257, train_joint.py:586-648): batch size 1
@@ -44,8 +54,7 @@ def model_forward(P, PS, qcfg, scfg, batch, weights, seg_token_idx, out_dim=256,
     images_sam = batch["images_sam"].float()
     B, T = images_sam.shape[:2]
     r = Q.forward(P, qcfg, batch["input_ids"], batch.get("attention_mask"), position_ids=batch.get("position_ids"), labels=batch["labels"],
-                  pixel_values_videos=batch["pixel_values_videos"].float(), video_grid_thw=batch["video_grid_thw"],
-                  second_per_grid_ts=batch.get("second_per_grid_ts"))
+                  second_per_grid_ts=batch.get("second_per_grid_ts"), **_vision(batch))
     ce_loss = r["loss"] * weights[0]
     mask = shifted_seg_mask(batch["labels"], seg_token_idx)
     pred = seg_embeddings(P, r["hidden"], mask)
@@ -96,8 +105,7 @@ def model_forward(P, PS, qcfg, scfg, batch, weights, seg_token_idx, out_dim=256,
 def evaluate(P, PS, qcfg, scfg, batch, seg_token_idx, original_size_list):
     """reference :325-393"""
     r = Q.forward(P, qcfg, batch["input_ids"], batch.get("attention_mask"), position_ids=batch.get("position_ids"),
-                  pixel_values_videos=batch["pixel_values_videos"].float(), video_grid_thw=batch["video_grid_thw"],
-                  second_per_grid_ts=batch.get("second_per_grid_ts"))
+                  second_per_grid_ts=batch.get("second_per_grid_ts"), **_vision(batch))
     mask = shifted_seg_mask(batch["input_ids"], seg_token_idx)
     pred = seg_embeddings(P, r["hidden"], mask)
     counts = mask.int().sum(-1)

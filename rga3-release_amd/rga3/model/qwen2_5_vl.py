@@ -20,6 +20,7 @@ MI355X-first choices (vs. the reference's per-op eager graph):
 from __future__ import annotations
 
 import contextlib
+from collections import OrderedDict
 
 import json
 import math
@@ -370,18 +371,28 @@ class VisionTransformer(nn.Module):
         self.patch_embed = VisionPatchEmbed(c)
         self.blocks = nn.ModuleList([VisionBlock(c) for _ in range(c.depth)])
         self.merger = PatchMerger(c.out_hidden_size, c.hidden_size, c.spatial_merge_size)
-        self._plans = {}
+        self._plans = OrderedDict()
 
     @property
     def dtype(self):
         return self.patch_embed.proj.weight.dtype
 
+    PLAN_CACHE_SIZE = 32
+
     def plan(self, grid_thw, device):
-        """Index plan for a grid (cached: grids repeat across steps)."""
+        """Index plan for a grid: window permutation, cu_seqlens, fp32 rotary tables in window order.
+
+        Cached, least recently used first out, at most PLAN_CACHE_SIZE grids (per device).  Video grids repeat from step to step and stay resident; image
+        grids change with every image size the data holds, and an unbounded cache would grow for the length of a run (a 7 252-patch 7B-dims image holds
+        4.6 MB of tables).  Every stream that reads an entry is remembered, and an evicted entry's tensors are recorded on those streams before they are
+        dropped (prefetch_vision reads plans on its side stream): the allocator does not hand their memory out again before that work is done."""
         c = self.config
         key = (tuple(map(tuple, np.asarray(grid_thw).reshape(-1, 3).tolist())), str(device))
-        if key in self._plans:
-            return self._plans[key]
+        plan = self._plans.get(key)
+        if plan is not None:
+            self._plans.move_to_end(key)
+            self._note_stream(plan)      # a hit may come from another stream than the one that built the entry (prefetch_vision's side stream, or back)
+            return plan
         g = np.asarray(grid_thw).reshape(-1, 3)
         wi, cu_win = QI.vision_window_index(g, c.spatial_merge_size, c.window_size, c.patch_size)
         cu_full = QI.vision_cu_seqlens(g)
@@ -397,9 +408,22 @@ class VisionTransformer(nn.Module):
         emb = torch.cat((rot, rot), dim=-1)
         plan = dict(window_index=wi_d, cu_win=torch.from_numpy(cu_win).to(device), cu_full=torch.from_numpy(cu_full).to(device),
                     max_win=int(np.diff(cu_win).max()), max_full=int(np.diff(cu_full).max()),
-                    cos=emb.cos().contiguous(), sin=emb.sin().contiguous(), n=int(pos.shape[0]))
+                    cos=emb.cos().contiguous(), sin=emb.sin().contiguous(), n=int(pos.shape[0]), streams=set())
+        self._note_stream(plan)
         self._plans[key] = plan
+        while len(self._plans) > self.PLAN_CACHE_SIZE:
+            _, old = self._plans.popitem(last=False)
+            for st in old["streams"]:
+                for t in old.values():
+                    if isinstance(t, torch.Tensor) and t.is_cuda:
+                        t.record_stream(st)
         return plan
+
+    @staticmethod
+    def _note_stream(plan):
+        dev = plan["window_index"].device
+        if dev.type == "cuda":
+            plan["streams"].add(torch.cuda.current_stream(dev))
 
     def forward(self, pixel_values, grid_thw):
         c = self.config

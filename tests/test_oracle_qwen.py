@@ -184,3 +184,106 @@ def test_storage_attention_core_rounds_like_the_fused_kernel():
         assert r(got, ref) < 1.2e-3, r(got, ref)
         assert r(eager, ref) > 2e-3 and r(eager, ref) > 2.5 * r(got, ref)
         assert r(plain, ref) > 1.2e-3                                              # fp32 mode: no rounding at all
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
+# IMAGE inputs (pixel_values / image_grid_thw) and batches that mix images and videos, pinned to tests/golden/qwen_image.npz
+# (tests/golden/make_qwen_image_fixtures.py: the installed transformers on the same tiny config and weights).  Same bounds as above.
+from tests.qwen_image import VIT_KEYS as IMG_KEYS, batch_pixels as _img_pixels, gold_image, vit_pixels  # noqa: E402
+
+
+@pytest.fixture(scope="module")
+def gimg():
+    return gold_image()
+
+
+@pytest.mark.parametrize("key", IMG_KEYS)
+def test_vision_index_plumbing_image_grids_bit_exact(gimg, key):
+    g = gimg[f"{key}_grid"]
+    wi, cw = Q.vision_window_index(g, 2, 112, 14)
+    assert np.array_equal(wi, gimg[f"{key}_window_index"])
+    assert np.array_equal(cw, gimg[f"{key}_cu_window"])
+    assert np.array_equal(Q.vision_cu_seqlens(g), gimg[f"{key}_cu_full"])
+    assert np.array_equal(Q.vision_position_ids(g, 2), gimg[f"{key}_pos_ids"])
+    if key == "big":
+        assert np.diff(gimg["big_cu_full"]).max() >= 1024            # the one full-attention segment is long enough for the split-KV route
+
+
+@pytest.mark.parametrize("key", IMG_KEYS)
+def test_vit_forward_image_grids(gimg, gold, key):
+    cfg, P = tiny_cfg(), tiny_params(gold)
+    g = gimg[f"{key}_grid"]
+    px = vit_pixels(gimg, key)
+    out, pre = Q.vit_forward(P, px, g, cfg, return_pre_merge=True)
+    assert np.abs(out.numpy() - gimg[f"{key}_pooler"]).max() < 1e-4
+    if f"{key}_last_hidden" in gimg.files:
+        assert np.abs(pre.numpy() - gimg[f"{key}_last_hidden"]).max() < 1e-4
+
+
+@pytest.mark.parametrize("rule", ["hf515", "hf449"])
+def test_rope_index_image_and_video_bit_exact(gimg, rule):
+    """row 0: text / image / text, right-padded; row 1: text / video / text / one-token image / text, left-padded.  The grids make both temporal rules agree."""
+    pos, delta = Q.rope_index(gimg["rope_img_input_ids"], tiny_cfg(), gimg["rope_img_image_grid"], gimg["rope_img_video_grid"], gimg["rope_img_spg"],
+                              gimg["rope_img_attention_mask"], temporal_rule=rule)
+    assert np.array_equal(pos, gimg["rope_img_position_ids"])
+    assert np.array_equal(delta, gimg["rope_img_deltas"])
+
+
+def test_product_rope_index_image_and_video_bit_exact(gimg):
+    """The product's host plumbing (rga3.model.qwen_index, what the GPU forward and generate() take their positions and deltas from) on the same batch."""
+    from rga3.model import qwen_index as QI
+
+    for rule in ("hf515", "hf449"):
+        pos, delta = QI.rope_index(gimg["rope_img_input_ids"], 301, 302, 2, 2, gimg["rope_img_image_grid"], gimg["rope_img_video_grid"], gimg["rope_img_spg"],
+                                   gimg["rope_img_attention_mask"], rule)
+        assert np.array_equal(pos, gimg["rope_img_position_ids"]) and np.array_equal(delta, gimg["rope_img_deltas"]), rule
+    for key in IMG_KEYS:
+        g = gimg[f"{key}_grid"]
+        wi, cw = QI.vision_window_index(g, 2, 112, 14)
+        assert np.array_equal(wi, gimg[f"{key}_window_index"]) and np.array_equal(cw, gimg[f"{key}_cu_window"]), key
+        assert np.array_equal(QI.vision_cu_seqlens(g), gimg[f"{key}_cu_full"]) and np.array_equal(QI.vision_position_ids(g, 2), gimg[f"{key}_pos_ids"]), key
+
+
+def test_full_forward_and_loss_image_and_video(gimg, gold):
+    """B = 2, padded: sample 0 image only (right-padded), sample 1 video then image (left-padded)."""
+    cfg, P = tiny_cfg(), tiny_params(gold)
+    px, pxv = _img_pixels(gimg, "mix")
+    r = Q.forward(P, cfg, torch.from_numpy(gimg["mix_input_ids"]), torch.from_numpy(gimg["mix_attention_mask"]), labels=torch.from_numpy(gimg["mix_labels"]),
+                  pixel_values=px, image_grid_thw=gimg["mix_image_grid"], pixel_values_videos=pxv, video_grid_thw=gimg["mix_video_grid"],
+                  second_per_grid_ts=np.array([1.0]))
+    assert np.array_equal(r["position_ids"].numpy(), gimg["mix_position_ids"])
+    am = gimg["mix_attention_mask"].astype(bool)
+    assert np.abs(r["hidden"].numpy() - gimg["mix_hidden_last"])[am].max() < 2e-4
+    assert np.abs(r["logits"].numpy() - gimg["mix_logits"])[am].max() < 2e-4
+    assert abs(float(r["loss"]) - float(gimg["mix_loss"])) < 1e-5
+
+
+def test_greedy_generate_fixtures_follow_the_oracle(gimg, gold):
+    """The greedy tokens HF produced for the image prompt and the left-padded image / video batch are the oracle's argmax over the teacher-forced sequence
+    (full-sequence forward: the decode positions follow from the prefill's rope deltas), on every step where the oracle's top-1 / top-2 margin is decisive."""
+    cfg, P = tiny_cfg(), tiny_params(gold)
+    cases = [("gen_img", _img_pixels(gimg, "gen_img", ("image",))[0], None, np.ones_like(gimg["gen_img_input_ids"]))]
+    px, pxv = _img_pixels(gimg, "gen_mix")
+    cases.append(("gen_mix", px, pxv, gimg["gen_mix_attention_mask"]))
+    for tag, px, pxv, am in cases:
+        full = gimg[f"{tag}_output_ids"]
+        S0 = gimg[f"{tag}_input_ids"].shape[1]
+        am_full = np.concatenate([am, np.ones((am.shape[0], full.shape[1] - S0), dtype=am.dtype)], 1)
+        r = Q.forward(P, cfg, torch.from_numpy(full), torch.from_numpy(am_full), pixel_values=px, image_grid_thw=gimg[f"{tag}_image_grid"],
+                      pixel_values_videos=pxv, video_grid_thw=gimg[f"{tag}_video_grid"] if pxv is not None else None,
+                      second_per_grid_ts=np.array([1.0]) if pxv is not None else None)
+        lg = r["logits"][:, S0 - 1:-1]
+        top2 = lg.topk(2, dim=-1).values
+        decided = (top2[..., 0] - top2[..., 1]) > 0.05 * lg.abs().amax(-1)
+        assert decided[:, 0].all(), tag
+        assert torch.equal(lg.argmax(-1)[decided], torch.from_numpy(full[:, S0:])[decided]), tag
+
+
+def test_unigr_oracle_vision_inputs_pass_through():
+    """oracle.unigr hands images and videos to the Qwen forward when the batch holds them, and leaves either out when it does not."""
+    from oracle import unigr as U
+
+    assert U._vision({"pixel_values_videos": torch.ones(2, 3, dtype=torch.float64), "video_grid_thw": "v"}).keys() == {"pixel_values_videos", "video_grid_thw"}
+    assert U._vision({"pixel_values": torch.ones(2, 3), "image_grid_thw": "i", "pixel_values_videos": None}).keys() == {"pixel_values", "image_grid_thw"}
+    both = U._vision({"pixel_values": torch.ones(2, 3, dtype=torch.bfloat16), "image_grid_thw": "i", "pixel_values_videos": torch.ones(1, 3), "video_grid_thw": "v"})
+    assert both["pixel_values"].dtype == torch.float32 and both["image_grid_thw"] == "i" and both["video_grid_thw"] == "v"

@@ -78,3 +78,39 @@ def object_masks(seg_flags, seed):
 
 
 CASES = {"11": (True, True), "10": (True, False), "00": (False, False)}
+
+
+def make_image_video_batch(video_seg, seed, image_grid=(1, 10, 14)):
+    """B = 2, padded: sample 0 is an IMAGE with [SEG] (pixel_values / image_grid_thw; right-padded) whose SAM input is its one frame repeated T_SAM times, as the
+    reference's image datasets feed it (reference utils/dataset.py:586-590, masks repeated alike); sample 1 is a video (pixel_values_videos / video_grid_thw) with or
+    without [SEG], built like make_batch's samples."""
+    from tests.blob_inputs import masks_at, object_video
+
+    g = np.random.default_rng(seed)
+    ni = image_grid[0] * (image_grid[1] // 2) * (image_grid[2] // 2)
+    nv = 2 * 4 * 6
+    seqs, labs = [], []
+    for b, (tok, n, has) in enumerate(((301, ni, True), (302, nv, video_seg))):
+        pre, ans = g.integers(0, 290, 6), g.integers(0, 290, 7)
+        if has:
+            ans[3] = SEG
+        seq = np.concatenate([pre, [303], np.full(n, tok), g.integers(0, 290, 4), ans]).astype(np.int64)
+        lab = np.full_like(seq, -100)
+        lab[-7:] = seq[-7:]
+        seqs.append(seq); labs.append(lab)
+    S = max(len(s) for s in seqs)
+    ids = np.zeros((2, S), np.int64); labels = np.full((2, S), -100, np.int64); am = np.zeros((2, S), np.int64)
+    for b in range(2):
+        ids[b, :len(seqs[b])], labels[b, :len(seqs[b])], am[b, :len(seqs[b])] = seqs[b], labs[b], 1
+    px = det_tensor(f"unigr_img_px_{seed}", (int(np.prod(image_grid)), 1176), 1.0, seed=5).to(torch.bfloat16).float()
+    pxv = det_tensor(f"unigr_px_{seed}_1", (2 * 8 * 12, 1176), 1.0, seed=5).to(torch.bfloat16).float()
+    still = object_video(f"unigr_still_{seed}", 1, SAM_SIDE, seed=6)
+    clip = object_video(f"unigr_img_{seed}_1", T_SAM, SAM_SIDE, seed=6)
+    imgs = torch.stack([still[0].expand(T_SAM, -1, -1, -1), clip[0]], 0).to(torch.bfloat16).float()
+    h, w = LABEL_HW
+    m_img = masks_at(still[1], (h, w)).expand(T_SAM, -1, -1).contiguous()
+    m_vid = masks_at(clip[1], (h, w))
+    return dict(input_ids=torch.from_numpy(ids), labels=torch.from_numpy(labels), attention_mask=torch.from_numpy(am),
+                pixel_values=px, image_grid_thw=torch.tensor([list(image_grid)]), pixel_values_videos=pxv, video_grid_thw=torch.tensor([[2, 8, 12]]),
+                second_per_grid_ts=torch.tensor([1.0]), images_sam=imgs, offset=torch.arange(3), masks_list=[m_img, m_vid if video_seg else m_vid[0:0]],
+                label_list=[torch.zeros(h, w) for _ in range(2)], resize_list=[(SAM_SIDE, SAM_SIDE)] * 2)
