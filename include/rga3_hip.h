@@ -49,15 +49,18 @@ int rga3_last_error(char* buf, size_t n);
  * colscale [N_out] is the ConvNeXt layer scale of reference model/sam2.py:690-703.
  * K, lda, ldw must be multiples of 8 (16-byte rows); tile = -1 lets the library choose (M <= 4 rows: the weight-stream kernel, 40; 5 - 16 rows: the token-row
  * kernel, 41).
- * Explicit tilings (all give the same bits except 22 / 32 / 25 / 14 / 40 / 41, whose K splits / lane-strided sums change the f32 summation order,
- * reproducibly):
+ * Explicit tilings (the authoritative list -- shape, kernel family and the entry points that take each id -- is the kTiles table of csrc/gemm_bf16.hip, which
+ * rga3_gemm_tiles reports; the paragraphs of the other GEMM entry points name their rga3_gemm_tiles entry instead of repeating ids).  All give the same bits
+ * except 22 / 26 / 32 / 25 / 14 / 40 / 41, whose K splits / lane-strided sums change the f32 summation order, reproducibly:
  *   20 = 256x256 ping-pong, one tile per workgroup;  21 = the same, persistent (one workgroup per CU);
  *   22 = persistent + stream-K tail (needs the caller workspace below);  27 / 26 = 21 / 22 whose last tile row, when it holds <= 64 rows (M = 2112 = 8 x 256 + 64),
  *   runs a quarter-work loop on workgroups of its own (as 21 / 22 for other M);  31 / 32 = 21 / 22 with 192x256 tiles (M = 2112 = 11 x 192);
  *   28 = 256x256 on FOUR waves (128x128 wave blocks, accumulators in the AGPRs, hand-ordered MFMA / fragment-read / LDS-DMA stream), one tile per workgroup,
  *        K a multiple of 64 (runs as 20 otherwise): bit-identical to 20, faster on long K (8192^3: 1 465 against 1 369 TFLOP/s), slower below K ~ 2000;
  *   25 = split-K for few output tiles over a very long K (same workspace; falls back to 21 when it does not apply);
- *   11, 12 / 3 / 4 / 5 / 13 = single-phase 128x128 / 128x256 / 128x320 / 128x192 / 64x64;  10 = single-phase 256x256 (first generation, A/B);
+ *   12 / 3 / 4 / 5 / 13 = single-phase 128x128 / 128x256 / 128x320 / 128x192 / 64x64 (under SwiGLU 4 / 5 / 7 run 128x256 tiles);  6 / 7 / 8 = 128x256 / 128x192 /
+ *        128x128 with three LDS stages;  10 = single-phase 256x256 (first generation, A/B);  11 = an alias of 12;
+ *   23 = 20 on 256x192 tiles for products without an activation (runs as 20 otherwise);
  *   14 = 64x64 with K cut into up to 32 slices (skinny plain products such as LoRA's x A^T: N = 128 over K = 3584; same workspace; runs as 13
  *        when there is a bias / activation / residual);
  *   40 = skinny weight-stream kernel for M <= 4 (the decode step of generate(), reference app.py:308-317): no column scale;
@@ -73,21 +76,21 @@ int rga3_gemm_bf16(const void* A, const void* W, const void* bias, const void* r
  *    1 / sqrt(row_sumsq_in[r] / 2^20 / norm_width + eps) before bias / activation (act as rga3_gemm_bf16, incl. SwiGLU);
  *  producer (row_sumsq_out != NULL): the sums of squares of the bf16 rows written to C are ADDED to row_sumsq_out[r] as 2^20 fixed-point integers by no-return
  *    integer atomics (the caller zeroes the array before the launch; any arrival order gives the same bits).
- * bf16 output, M > 16, tiles with the shared epilogue (not 14 / 25 / 40 / 41). */
+ * bf16 output, M > 16, tiles with the shared epilogue (rga3_gemm_tiles entry 1: every tiling of rga3_gemm_bf16 without an epilogue of its own). */
 int rga3_gemm_rms_bf16(const void* A, const void* W, const void* bias, const void* residual, void* C, int64_t M, int64_t N, int64_t K, int64_t lda,
                        int64_t ldw, int64_t ldc, int64_t ldr, int act, int tile, void* workspace, int64_t workspace_bytes, const uint64_t* row_sumsq_in,
                        int64_t norm_width, float eps, uint64_t* row_sumsq_out, void* stream);
 /* RGA3_ACT_SWIGLU product that also stores its pre-activations (round 4; training forward of the decoder MLP -- HF Qwen2MLP under autograd, reference
  * train_joint.py:534): C [M, N / 2] = silu(gate) * up, pre [M, N] (row stride ldpre) = the interleaved gate | up linear outputs rounded to bf16, which the backward
- * of the activation reads (rga3_swiglu_bwd).  Replaces rga3_gemm_bf16 (plain) + rga3_swiglu_fwd. */
+ * of the activation reads (rga3_swiglu_bwd).  Replaces rga3_gemm_bf16 (plain) + rga3_swiglu_fwd.  M > 4; tiles as rga3_gemm_bf16 with SwiGLU. */
 int rga3_gemm_swiglu_pre_bf16(const void* A, const void* W, const void* bias, void* C, void* pre, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldw,
                               int64_t ldc, int64_t ldpre, int tile, void* workspace, int64_t workspace_bytes, void* stream);
 /* Concatenated operands (round 4): LoRA's low-rank products folded into the frozen products of a decoder layer (PEFT LoRA layer, reference train_joint.py:193-232,
  * run_torchrun.sh:30-31; y = W x + s B A dropout(x)).
  *   K side (A2 [M, K2], W2 [N, K2]):  C [M, N] = [A | A2] . [W | W2]^T (+ bias)      forward:  qkv = h W^T + [t_q | t_v] [B_q 0; 0 0; 0 B_v]^T as ONE product
  *   N side (Wn [N2, K], Cn [M, N2]):  also Cn = A . Wn^T from the same launch        backward: [dh | dt_q | dt_v] = dqkv [W | sB_q | sB_v]
- * bf16, no activation; K, K2 multiples of 64; with an N side N must be a multiple of the tile width.  tile: -1 / 12 (128 x 128), 3 / 6 (128 x 256), 13 (64 x 64); K side
- * only: also 4 (128 x 320), 5 (128 x 192).  Single-phase kernels (no workspace). */
+ * bf16, no activation; K, K2 multiples of 64; with an N side N must be a multiple of the tile width.  tile: -1 (= 12) or a single-phase tiling of rga3_gemm_tiles
+ * entry 5 with an N side, entry 4 (which adds the widths that need no N side: 128 x 320, 128 x 192) without.  No workspace. */
 int rga3_gemm_cat_bf16(const void* A, const void* W, const void* bias, void* C, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldw, int64_t ldc,
                        const void* A2, const void* W2, int64_t K2, int64_t lda2, int64_t ldw2, const void* Wn, void* Cn, int64_t N2, int64_t ldwn, int64_t ldcn,
                        int tile, void* stream);
@@ -155,7 +158,8 @@ int rga3_layernorm_fwd(const void* x, const void* weight, const void* bias, void
 /* LayerNorm folded into the consuming product (Hiera norm1 -> qkv, norm2 -> fc1, reference model/sam2.py:1035-1117): rga3_layernorm_stats writes
  * stats [rows][2] f32 = (mean, 1/sqrt(var + eps)) -- one read of x instead of LayerNorm's read + write -- and rga3_gemm_ln_bf16 computes
  * C = act(LayerNorm(A) W^T + b) as rinv_r (A Wf^T - mean_r c_n) + bias_n with Wf = W diag(gamma) (bf16), colc_n = sum_k Wf_nk (f32), bias = beta W^T + b (bf16).
- * act none / gelu / relu; tile -1 or 3 / 5 / 12 / 13 / 20 (see rga3_gemm_bf16); K % 8 == 0, N % 4 == 0. */
+ * act none / gelu / relu; tile -1 (= 12) or one of rga3_gemm_tiles entry 2 (20, the single-phase 3 / 5 / 12 / 13 and their three-stage forms 6 / 7); K % 8 == 0,
+ * N % 4 == 0. */
 int rga3_layernorm_stats(const void* x, float* stats, int64_t rows, int64_t dim, int64_t ldx, float eps, void* stream);
 int rga3_gemm_ln_bf16(const void* A, const void* Wf, const void* bias, const float* colc, const float* rowstat, void* C, int64_t M, int64_t N, int64_t K,
                       int64_t lda, int64_t ldw, int64_t ldc, int act, int tile, void* stream);
@@ -163,10 +167,11 @@ int rga3_gemm_ln_bf16(const void* A, const void* Wf, const void* bias, const flo
  * norm2 reads, and x = x + mlp(norm2(x)), which the next block's norm1 reads (reference model/sam2.py:1085-1117) -- leave, per output row r and TILE COLUMN t,
  *   row_parts[r][t] = (sum, sum of squares) of the bf16 values written to row r inside tile column t          (f32 pairs, [M][slices][2])
  * with slices = rga3_gemm_lnsum_slices(N, tile).  Plain stores, each element written exactly once (the waves of a workgroup combine through LDS in wave order): no
- * atomics, nothing to zero, bitwise reproducible.  rga3_gemm_lnsum_bf16 = rga3_gemm_bf16 (bf16 output, M > 16, no activation, tiles -1 / 3 / 5 / 12 / 13 / 20 / 23:
+ * atomics, nothing to zero, bitwise reproducible.  rga3_gemm_lnsum_bf16 = rga3_gemm_bf16 (bf16 output, M > 16, no activation, tile -1 (= 12) or one of rga3_gemm_tiles
+ * entry 3; rga3_gemm_lnsum_slices = ceil(N / tile width), -1 for any other tile:
  * single-pass kernels instantiated for this epilogue, so no other product's kernel changes) with that output; rga3_gemm_lnq_bf16 = rga3_gemm_ln_bf16 reading such
  * partial sums (norm_width = the row width they cover, eps the LayerNorm's; the partials of a row are added, and mean and the biased variance S2 / w - mean^2
- * formed, in f64 inside the kernel).  Together they replace the stand-alone rga3_layernorm_stats pass over the rows. */
+ * formed, in f64 inside the kernel; tiles as rga3_gemm_ln_bf16).  Together they replace the stand-alone rga3_layernorm_stats pass over the rows. */
 int64_t rga3_gemm_lnsum_slices(int64_t N, int tile);
 int rga3_gemm_lnsum_bf16(const void* A, const void* W, const void* bias, const void* residual, void* C, int64_t M, int64_t N, int64_t K, int64_t lda,
                          int64_t ldw, int64_t ldc, int64_t ldr, int tile, float* row_parts, void* stream);
@@ -341,6 +346,11 @@ int64_t rga3_gemm_timeout_counter_offset(void);
  * ragged (more than 64 rows) or no plan applies (the tiles then run as 22 / 21); < 0 = bad arguments.  No reference counterpart (the reference's GEMMs are vendor
  * BLAS calls); exists so that what the kernel's hand-off relies on is testable without a GPU. */
 int rga3_gemm_ragged_plan(int64_t M, int64_t N, int64_t K, int cus, int split, int* plan, unsigned* start);
+/* Host only: the tilings an entry point has kernels for, in the order a tuner should try them.  entry: 0 rga3_gemm_bf16 / rga3_gemm_swiglu_pre_bf16, 1 rga3_gemm_rms_bf16,
+ * 2 rga3_gemm_ln_bf16 / rga3_gemm_lnq_bf16, 3 rga3_gemm_lnsum_bf16, 4 / 5 rga3_gemm_cat_bf16 with a K side only / with an N side.  Fills the first `cap` entries of
+ * ids / bm / bn (tile id, tile rows, tile columns) and returns the number of tilings (so cap = 0 asks for the count); < 0 on an unknown entry.  The entry points
+ * validate their `tile` argument against the same table. */
+int rga3_gemm_tiles(int entry, int* ids, int* bm, int* bn, int cap);
 /* (the 32-bit word BEHIND that counter is a fault-injection switch for tests: 0 in every real run -- the caller zeroes the flag page; 0xffffffff makes every stream-K
  * owner behave as if its contributors never publish; any other value is the spin limit) */
 /* dx = d rmsnorm(x; weight)/dx . dy (+ add): backward of HF Qwen2_5_VLRMSNorm (modeling_qwen2_5_vl.py:74-79) w.r.t. x */

@@ -2698,42 +2698,145 @@ static int pick_tile(int M, int N, int K, bool plain, int forced) {
     return ids[best];
 }
 
-template <int ACT, bool OUT_F32>
-static int launch_act(const GemmArgs& a, int tile, hipStream_t st) {
-    switch (tile) {
-        case 3: return launch_cfg<128, 256, 2, 4, ACT, OUT_F32, 0>(a, st);
-        case 4:  // 128x320: N = 1280 (ViT proj / fc2) at M = 8192 is exactly 256 tiles; 5 n-tiles per wave, so no SwiGLU pairs
-            if constexpr (ACT != ACT_SWIGLU) return launch_cfg<128, 320, 2, 4, ACT, OUT_F32, 0>(a, st);
-            else return launch_cfg<128, 256, 2, 4, ACT, OUT_F32, 0>(a, st);
-        case 5:   // 128x192: N = 576 = 3 x 192 (Hiera stage-3 proj / fc2 outputs: 2.25 tiles of 256 otherwise); 3 n-tiles per wave, so no SwiGLU pairs
-            if constexpr (ACT != ACT_SWIGLU) return launch_cfg<128, 192, 2, 4, ACT, OUT_F32, 0>(a, st);
-            else return launch_cfg<128, 256, 2, 4, ACT, OUT_F32, 0>(a, st);
-        case 6: return launch_cfg<128, 256, 2, 4, ACT, OUT_F32, 3>(a, st);   // 128x256, three LDS stages (144 KiB): two K-tiles in flight (cold weights)
-        case 7:   // 128x192, three stages (120 KiB, one workgroup per CU)
-            if constexpr (ACT != ACT_SWIGLU) return launch_cfg<128, 192, 2, 4, ACT, OUT_F32, 3>(a, st);
-            else return launch_cfg<128, 256, 2, 4, ACT, OUT_F32, 3>(a, st);
-        case 8: return launch_cfg<128, 128, 2, 2, ACT, OUT_F32, 3>(a, st);   // 128x128 on 4 waves, three stages (96 KiB)
-        case 10: return launch_cfg<256, 256, 2, 4, ACT, OUT_F32, 0>(a, st);
-        case 13: return launch_cfg<64, 64, 2, 2, ACT, OUT_F32, 0>(a, st);   // small products (SAM2 per-frame 4096 x 256 x 256: 256 tiles instead of 64)
-        case 14:   // 64 x 64 with a K split (skinny plain products)
-            if constexpr (ACT == ACT_NONE) return launch_split64<OUT_F32>(a, st);
-            else return launch_cfg<64, 64, 2, 2, ACT, OUT_F32, 0>(a, st);
-        case 20: return launch_pp<ACT, OUT_F32>(a, st);
-        case 23:   // ping-pong on 256 x 192 tiles (4 x 2 wave grid, 6 n-tiles per wave: SwiGLU pairs exist, but its packed widths are multiples of 256 anyway)
-            if constexpr (ACT == ACT_NONE) return launch_pp<ACT, OUT_F32, false, true>(a, st);
-            else return launch_pp<ACT, OUT_F32>(a, st);
-        case 21: return launch_sk<ACT, OUT_F32>(a, false, st);
-        case 22: return launch_sk<ACT, OUT_F32>(a, true, st);
-        case 26: return launch_sk<ACT, OUT_F32>(a, true, st, true);    // 22 / 21 whose ragged last tile row (<= 64 rows: M = 2112 = 8 x 256 + 64) runs the quarter-work loop
-        case 27: return launch_sk<ACT, OUT_F32>(a, false, st, true);   //   on workgroups of its own
-        case 31: return launch_sk<ACT, OUT_F32, 3>(a, false, st);   // 192 x 256 tiles, persistent
-        case 32: return launch_sk<ACT, OUT_F32, 3>(a, true, st);    // ... + stream-K tail
-        case 25: return launch_splitk<ACT, OUT_F32>(a, st);
-        case 28: return launch_w4<ACT, OUT_F32>(a, st);   // 256 x 256 on four waves (128 x 128 wave blocks, AGPR accumulators), one tile per workgroup
-        case 40: return launch_gemv<ACT, OUT_F32>(a, st);   // M <= 4: weight stream (decode step)
-        case 41: return launch_rows16<ACT, OUT_F32>(a, st);  // 5 <= M <= 16 token rows
-        default: return launch_cfg<128, 128, 2, 2, ACT, OUT_F32, 0>(a, st);
+// ---- The tilings.  One row per tile id: which kernel family runs it, its shape, and which entry points have a kernel for it.  Every validity check, the dispatch
+// (launch_tile), rga3_gemm_lnsum_slices and rga3_gemm_tiles (from which rga3.hip.ops takes its candidate lists) read this table: a new tiling is a new row.
+// Families: F_SINGLE gemm_nt_kernel (one tile per workgroup, one barrier phase per K-tile); F_PP gemm_nt_pp_kernel (ping-pong on eight waves, one tile per workgroup);
+// F_SK gemm_nt_sk_kernel (persistent: one workgroup per CU; Tile::sk adds the stream-K tail / the ragged-row loop); F_SPLITK split-K for few tiles over a very long K
+// (falls back to F_SK / F_PP where it does not apply); F_SPLIT64 64 x 64 with a K split (plain products; anything else runs as the single-phase 64 x 64); F_W4 256 x 256
+// on four waves; F_GEMV the weight stream for M <= 4; F_ROWS16 token rows, M <= 16.
+enum TileFamily { F_SINGLE, F_PP, F_SK, F_SPLITK, F_SPLIT64, F_W4, F_GEMV, F_ROWS16 };
+enum { SK_TAIL = 1, SK_RAGGED = 2 };
+// Entry points (rga3_gemm_tiles' `entry` is the bit's index): E_PLAIN rga3_gemm_bf16 (and rga3_gemm_swiglu_pre_bf16, whose only limits are those of tiles 40 / 41);
+// E_SHARED rga3_gemm_rms_bf16 (the tile ends in gemm_epilogue, not in an epilogue of its own); E_LN rga3_gemm_ln_bf16 / rga3_gemm_lnq_bf16 (kernels instantiated with
+// LNF = 1); E_LNSUM rga3_gemm_lnsum_bf16 (LNF = 2); E_CATK / E_CATN rga3_gemm_cat_bf16 with a K side only / with an N side.
+enum : unsigned { E_PLAIN = 1, E_SHARED = 2, E_LN = 4, E_LNSUM = 8, E_CATK = 16, E_CATN = 32 };
+constexpr int kNumEntries = 6;
+struct Tile {
+    int id;
+    TileFamily fam;
+    int bm, bn, stages;   // stages: of LDS (F_SINGLE: 3 = two K-tiles in flight)
+    unsigned entries;
+    int swiglu_bn;     // F_SINGLE with an odd number of n-tiles per wave (no gate | up pairs): the BN it runs under SwiGLU; 0 = its own
+    int sk;            // F_SK: SK_TAIL | SK_RAGGED
+};
+constexpr unsigned PS = E_PLAIN | E_SHARED;
+constexpr Tile kTiles[] = {
+    {3, F_SINGLE, 128, 256, 2, PS | E_LN | E_LNSUM | E_CATK | E_CATN, 0, 0},
+    {4, F_SINGLE, 128, 320, 2, PS | E_CATK, 256, 0},            // N = 1280 (ViT proj / fc2) at M = 8192 is exactly 256 tiles
+    {5, F_SINGLE, 128, 192, 2, PS | E_LN | E_LNSUM | E_CATK, 256, 0},   // N = 576 = 3 x 192 (Hiera stage-3 proj / fc2 outputs: 2.25 tiles of 256 otherwise)
+    {6, F_SINGLE, 128, 256, 3, PS | E_LN | E_CATK | E_CATN, 0, 0},      // 144 KiB of LDS (cold weights)
+    {7, F_SINGLE, 128, 192, 3, PS | E_LN, 256, 0},              // 120 KiB, one workgroup per CU
+    {8, F_SINGLE, 128, 128, 3, PS, 0, 0},                       // 96 KiB
+    {10, F_SINGLE, 256, 256, 2, PS, 0, 0},
+    {11, F_SINGLE, 128, 128, 2, PS, 0, 0},                      // an ALIAS of 12: pick_tile scores this id as a single-phase 256 x 128, a kernel the library does not have
+    {12, F_SINGLE, 128, 128, 2, PS | E_LN | E_LNSUM | E_CATK | E_CATN, 0, 0},   // also what tile = -1 means to the entry points without a heuristic
+    {13, F_SINGLE, 64, 64, 2, PS | E_LN | E_LNSUM | E_CATK | E_CATN, 0, 0},     // small products (SAM2 per-frame 4096 x 256 x 256: 256 tiles instead of 64)
+    {14, F_SPLIT64, 64, 64, 2, E_PLAIN, 0, 0},                  // skinny plain products
+    {20, F_PP, 256, 256, 2, PS | E_LN | E_LNSUM, 0, 0},
+    {21, F_SK, 256, 256, 2, PS, 0, 0},
+    {22, F_SK, 256, 256, 2, PS, 0, SK_TAIL},
+    {23, F_PP, 256, 192, 2, PS | E_LNSUM, 0, 0},                // 4 x 2 wave grid; without an activation only (runs as 20 otherwise: SwiGLU's packed widths are multiples of 256 anyway)
+    {25, F_SPLITK, 256, 256, 2, E_PLAIN, 0, 0},
+    {26, F_SK, 256, 256, 2, PS, 0, SK_TAIL | SK_RAGGED},        // 22 / 21 whose ragged last tile row (<= 64 rows: M = 2112 = 8 x 256 + 64) runs the quarter-work loop
+    {27, F_SK, 256, 256, 2, PS, 0, SK_RAGGED},                  //   on workgroups of its own
+    {28, F_W4, 256, 256, 2, PS, 0, 0},                          // 128 x 128 wave blocks, AGPR accumulators, one tile per workgroup
+    {31, F_SK, 192, 256, 2, PS, 0, 0},
+    {32, F_SK, 192, 256, 2, PS, 0, SK_TAIL},
+    {40, F_GEMV, 4, 16, 0, E_PLAIN, 0, 0},                      // decode step
+    {41, F_ROWS16, 16, 16, 0, E_PLAIN, 0, 0},                   // 5 <= M <= 16
+};
+constexpr int kNumTiles = (int)(sizeof(kTiles) / sizeof(kTiles[0]));
+
+// rga3_gemm_tiles lists an entry point's tilings in the order the tuner is to try them (rga3.hip.tuner.pick times the candidates in the order given): that order is
+// behaviour, and no single row order serves all four.  E_PLAIN / E_SHARED come in row order.
+constexpr int kOrderLn[] = {20, 3, 5, 12, 13, 6, 7};
+constexpr int kOrderLnsum[] = {20, 3, 5, 12, 13, 23};
+constexpr int kOrderCatK[] = {12, 3, 4, 5, 6, 13};
+constexpr int kOrderCatN[] = {12, 3, 6, 13};
+struct TileOrder { const int* ids; int n; };
+constexpr TileOrder kOrders[kNumEntries] = {{nullptr, 0}, {nullptr, 0}, {kOrderLn, 7}, {kOrderLnsum, 6}, {kOrderCatK, 6}, {kOrderCatN, 4}};
+
+constexpr bool order_matches_table(int entry) {   // an order list names, once each, exactly the rows that carry the entry's bit
+    int rows = 0;
+    for (const Tile& t : kTiles) {
+        int listed = 0;
+        for (int i = 0; i < kOrders[entry].n; ++i) listed += kOrders[entry].ids[i] == t.id;
+        if (listed != (int)((t.entries >> entry) & 1)) return false;
+        rows += listed;
     }
+    return rows == kOrders[entry].n;
+}
+static_assert(order_matches_table(2) && order_matches_table(3) && order_matches_table(4) && order_matches_table(5), "kOrder* and kTiles disagree");
+
+// The row of tile `id` when the entry point has a kernel for it, else null.  -1 is tile 12 (rga3_gemm_bf16 alone replaces it by pick_tile's choice).
+static const Tile* find_tile(int id, unsigned entry) {
+    if (id == -1) id = 12;
+    for (const Tile& t : kTiles)
+        if (t.id == id) return (t.entries & entry) ? &t : nullptr;
+    return nullptr;
+}
+
+// The one dispatch: the launcher of tile `tile` for (activation, output type, LayerNorm mode LNF: 0 none, 1 folded consumer, 2 statistics producer).  A (tile, LNF) pair
+// without the entry bit instantiates no kernel.
+template <int ACT, bool OUT_F32, int LNF, int I = 0>
+static int launch_tile(const GemmArgs& a, int tile, hipStream_t st) {
+    if constexpr (I == kNumTiles) {
+        return fail(RGA3_EINVAL, "gemm: tile %d", tile);
+    } else if (kTiles[I].id != tile) {
+        return launch_tile<ACT, OUT_F32, LNF, I + 1>(a, tile, st);
+    } else {
+        constexpr Tile t = kTiles[I];
+        if constexpr (!(t.entries & (LNF == 1 ? E_LN : LNF == 2 ? E_LNSUM : E_PLAIN))) {
+            return fail(RGA3_EINVAL, "gemm: tile %d has no kernel for this entry point", tile);
+        } else if constexpr (t.fam == F_SINGLE) {
+            constexpr int BN = (ACT == ACT_SWIGLU && t.swiglu_bn) ? t.swiglu_bn : t.bn;
+            return launch_cfg<t.bm, BN, 2, (BN >= 192 ? 4 : 2), ACT, OUT_F32, (t.stages == 3 ? 3 : 0), LNF>(a, st);
+        } else if constexpr (t.fam == F_PP) {
+            if constexpr (t.bn == 192 && ACT == ACT_NONE) return launch_pp<ACT, OUT_F32, LNF, true>(a, st);
+            else return launch_pp<ACT, OUT_F32, LNF>(a, st);
+        } else if constexpr (t.fam == F_SK) {
+            return launch_sk<ACT, OUT_F32, t.bm / 64>(a, (t.sk & SK_TAIL) != 0, st, (t.sk & SK_RAGGED) != 0);
+        } else if constexpr (t.fam == F_SPLITK) {
+            return launch_splitk<ACT, OUT_F32>(a, st);
+        } else if constexpr (t.fam == F_SPLIT64) {
+            if constexpr (ACT == ACT_NONE) return launch_split64<OUT_F32>(a, st);
+            else return launch_cfg<t.bm, t.bn, 2, 2, ACT, OUT_F32, 0>(a, st);
+        } else if constexpr (t.fam == F_W4) {
+            return launch_w4<ACT, OUT_F32>(a, st);
+        } else if constexpr (t.fam == F_GEMV) {
+            return launch_gemv<ACT, OUT_F32>(a, st);
+        } else {
+            return launch_rows16<ACT, OUT_F32>(a, st);
+        }
+    }
+}
+
+// What every NT entry point checks and fills (`who` prefixes the messages); the entry point adds its own fields and bounds.
+static int nt_args(GemmArgs& a, const char* who, const void* A, const void* W, const void* bias, const void* residual, void* C, int64_t M, int64_t N, int64_t K,
+                   int64_t lda, int64_t ldw, int64_t ldc, int64_t ldr) {
+    RGA3_CHECK_ARG(A && W && C, "%s: null pointer", who);
+    RGA3_CHECK_ARG(lda % 8 == 0 && ldw % 8 == 0, "%s: lda/ldw must be multiples of 8 elements (16-byte rows)", who);
+    RGA3_CHECK_ARG((((uintptr_t)A | (uintptr_t)W | (uintptr_t)C) & 15) == 0, "%s: pointers must be 16-byte aligned", who);
+    RGA3_CHECK_ARG(M * lda < (1LL << 32) && N * ldw < (1LL << 32), "%s: operands must be < 2^32 elements (32-bit staging offsets)", who);
+    a = GemmArgs{};
+    a.A = (const unsigned short*)A; a.W = (const unsigned short*)W; a.C = C;
+    a.bias = (const unsigned short*)bias; a.res = (const unsigned short*)residual;
+    a.M = (int)M; a.N = (int)N; a.K = (int)K;
+    a.lda = lda; a.ldw = ldw; a.ldc = ldc; a.ldr = ldr;
+    return 0;
+}
+
+// K slices of a TN product (A^T B over 128 x 128 output tiles, K-tiles of 32): few output tiles over many tokens (LoRA dW: 1 x 28 tiles, K = 2112 / 4160; mask-path dW:
+// 1 - 4 tiles, K = 65 536 ..) are cut into Z slices, one workgroup each, whose f32 partial slabs are summed in fixed order (deterministic; no atomics).  At most the
+// slabs that fit ws_bytes (INT64_MAX: unbounded); 1 = no split.
+static int tn_slices(int64_t M, int64_t N, int64_t K, int64_t ws_bytes) {
+    const int64_t tiles = cdiv(M, 128) * cdiv(N, 128), nk = cdiv(K, 32), fit = ws_bytes / (M * N * 4);
+    if (tiles >= 128 || nk < 32) return 1;
+    int64_t Z = 256 / tiles;
+    if (Z > 64) Z = 64;   // (16 until round 2: per-pixel weight gradients of the mask path, 1-4 tiles over 65 536 - 262 144 rows, filled 64 CUs)
+    if (Z > nk / 8) Z = nk / 8;
+    if (Z > fit) Z = fit;
+    return Z < 2 ? 1 : (int)Z;
 }
 
 }  // namespace rga3
@@ -2810,10 +2913,52 @@ extern "C" int64_t rga3_gemm_timeout_counter_offset(void) {
     return (int64_t)cus * 4;
 }
 
+// Host only (no device needed): the tilings an entry point has kernels for, in the order the tuner is to try them.  entry: 0 rga3_gemm_bf16, 1 rga3_gemm_rms_bf16 (the
+// shared epilogue), 2 rga3_gemm_ln_bf16 / rga3_gemm_lnq_bf16, 3 rga3_gemm_lnsum_bf16, 4 / 5 rga3_gemm_cat_bf16 with a K side only / with an N side.  Fills the first
+// `cap` of ids / bm / bn (tile id, tile rows, tile columns) and returns the number of tilings; < 0 on bad arguments.  The entry points validate `tile` against the same rows.
+extern "C" int rga3_gemm_tiles(int entry, int* ids, int* bm, int* bn, int cap) {
+    RGA3_CHECK_ARG(entry >= 0 && entry < kNumEntries && cap >= 0 && (cap == 0 || (ids && bm && bn)), "gemm_tiles: entry %d (0..%d), cap %d", entry, kNumEntries - 1, cap);
+    const TileOrder& o = kOrders[entry];
+    int n = 0;
+    for (int i = 0; i < (o.n ? o.n : kNumTiles); ++i)
+        if (const Tile* t = find_tile(o.n ? o.ids[i] : kTiles[i].id, 1u << entry)) {   // (no order list: the rows that carry the bit, in row order)
+            if (n < cap) { ids[n] = t->id; bm[n] = t->bm; bn[n] = t->bn; }
+            ++n;
+        }
+    return n;
+}
+
 static int gemm_bf16_impl(const void* A, const void* W, const void* bias, const void* residual, const void* colscale, void* C,
                           int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldw, int64_t ldc, int64_t ldr,
                           int act, int out_dtype, int tile, void* workspace, int64_t workspace_bytes, const unsigned long long* rs_in, int64_t rs_width, float rs_eps,
-                          unsigned long long* rs_out, void* stream, void* pre = nullptr, int64_t ldpre = 0);
+                          unsigned long long* rs_out, void* stream, void* pre = nullptr, int64_t ldpre = 0) {
+    RGA3_CHECK_ARG(!pre || (act == ACT_SWIGLU && M > 4 && (((uintptr_t)pre) & 15) == 0 && ldpre >= N), "gemm: the pre-activation output goes with the SwiGLU tile epilogues (M > 4)");
+    RGA3_CHECK_ARG(M > 0 && N > 0 && K > 0, "gemm: bad shape M=%ld N=%ld K=%ld", (long)M, (long)N, (long)K);
+    RGA3_CHECK_ARG(K % 8 == 0, "gemm: K=%ld must be a multiple of 8 (16-byte staging chunks)", (long)K);
+    RGA3_CHECK_ARG(out_dtype == RGA3_BF16 || out_dtype == RGA3_F32, "gemm: out_dtype %d", out_dtype);
+    RGA3_CHECK_ARG(act >= 0 && act <= 3, "gemm: act %d", act);
+    RGA3_CHECK_ARG(!(out_dtype == RGA3_F32 && (act != ACT_NONE || residual || colscale)), "gemm: f32 output supports bias only");
+    RGA3_CHECK_ARG(act != ACT_SWIGLU || N % 32 == 0, "gemm: swiglu needs N %% 32 == 0");
+    RGA3_CHECK_ARG(find_tile(tile, E_PLAIN), "gemm: tile %d", tile);
+    GemmArgs a;
+    if (int rc = nt_args(a, "gemm", A, W, bias, residual, C, M, N, K, lda, ldw, ldc, ldr)) return rc;
+    a.colscale = (const unsigned short*)colscale;
+    a.ws = workspace; a.ws_bytes = workspace_bytes;
+    a.rs_in = rs_in; a.rs_in_scale = rs_in ? 1.0f / (kRowSumFix * (float)rs_width) : 0.f; a.rs_eps = rs_eps; a.rs_out = rs_out;
+    a.pre = (unsigned short*)pre; a.ldpre = ldpre;
+    hipStream_t st = (hipStream_t)stream;
+    RGA3_CHECK_ARG(tile != 40 || (M <= 4 && !colscale), "gemm: the skinny kernel (tile 40) takes M <= 4 rows and no column scale");
+    const bool rows16_ok = M <= 16 && !colscale && out_dtype == RGA3_BF16 && act != ACT_SWIGLU;
+    RGA3_CHECK_ARG(tile != 41 || rows16_ok, "gemm: the token-row kernel (tile 41) takes M <= 16 rows, bf16 output, no column scale, no SwiGLU");
+    int tl = (tile == -1 && M <= 4 && !colscale) ? 40 : (tile == -1 && rows16_ok) ? 41 : pick_tile((int)M, (int)N, (int)K, act == ACT_NONE && !residual && !colscale && !rs_in && !rs_out, tile);   // row sums live in the shared epilogue: never the split-K tile
+    if (out_dtype == RGA3_F32) return launch_tile<ACT_NONE, true, 0>(a, tl, st);
+    switch (act) {
+        case ACT_NONE: return launch_tile<ACT_NONE, false, 0>(a, tl, st);
+        case ACT_GELU: return launch_tile<ACT_GELU, false, 0>(a, tl, st);
+        case ACT_SWIGLU: return launch_tile<ACT_SWIGLU, false, 0>(a, tl, st);
+        default: return launch_tile<ACT_RELU, false, 0>(a, tl, st);
+    }
+}
 
 extern "C" int rga3_gemm_bf16(const void* A, const void* W, const void* bias, const void* residual, const void* colscale, void* C,
                               int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldw, int64_t ldc, int64_t ldr,
@@ -2825,15 +2970,15 @@ extern "C" int rga3_gemm_bf16(const void* A, const void* W, const void* bias, co
 // :602-757 and :211-321).  Consumer side (row_sumsq_in): A holds the UN-normalised rows x, W the weight with the norm weight folded in (W' = W diag(gamma)), and
 //   RMSNorm(x) W^T = rinv_r (x W'^T),  rinv_r = 1 / sqrt(row_sumsq_in[r] / 2^20 / norm_width + eps)
 // is applied to the accumulators before bias / activation.  Producer side (row_sumsq_out): the sums of squares of the bf16 output rows are ADDED to
-// row_sumsq_out[r] as fixed-point integers (the caller zeroes it; integer atomics: any arrival order gives the same bits).  bf16 output only; tiles whose
-// epilogue is the shared one (not 14 / 25 / 40 / 41).
+// row_sumsq_out[r] as fixed-point integers (the caller zeroes it; integer atomics: any arrival order gives the same bits).  bf16 output; tiles whose
+// epilogue is the shared one (E_SHARED).
 extern "C" int rga3_gemm_rms_bf16(const void* A, const void* W, const void* bias, const void* residual, void* C, int64_t M, int64_t N, int64_t K, int64_t lda,
                                   int64_t ldw, int64_t ldc, int64_t ldr, int act, int tile, void* workspace, int64_t workspace_bytes, const uint64_t* row_sumsq_in,
                                   int64_t norm_width, float eps, uint64_t* row_sumsq_out, void* stream) {
     RGA3_CHECK_ARG(row_sumsq_in || row_sumsq_out, "gemm_rms: neither row_sumsq_in nor row_sumsq_out given (use rga3_gemm_bf16)");
     RGA3_CHECK_ARG(!row_sumsq_in || (norm_width > 0 && eps >= 0.f), "gemm_rms: norm_width %ld eps %g", (long)norm_width, (double)eps);
     RGA3_CHECK_ARG((((uintptr_t)row_sumsq_in | (uintptr_t)row_sumsq_out) & 7) == 0, "gemm_rms: row sums must be 8-byte aligned");
-    RGA3_CHECK_ARG(tile != 14 && tile != 25 && tile != 40 && tile != 41, "gemm_rms: tile %d has its own epilogue", tile);
+    RGA3_CHECK_ARG(find_tile(tile, E_SHARED), "gemm_rms: tile %d has no kernel with the shared epilogue", tile);
     RGA3_CHECK_ARG(M > 16, "gemm_rms: M %ld (token-row products take the unfused route)", (long)M);
     return gemm_bf16_impl(A, W, bias, residual, nullptr, C, M, N, K, lda, ldw, ldc, ldr, act, RGA3_BF16, tile, workspace, workspace_bytes,
                           (const unsigned long long*)row_sumsq_in, norm_width, eps, (unsigned long long*)row_sumsq_out, stream);
@@ -2842,36 +2987,21 @@ extern "C" int rga3_gemm_rms_bf16(const void* A, const void* W, const void* bias
 // rga3_gemm_bf16 whose epilogue also leaves the LayerNorm statistics of the rows it writes (Hiera MultiScaleBlock: x = shortcut + proj(attn) feeds norm2, x = x + mlp(..)
 // feeds the next block's norm1; reference sam2.py:1085-1117): row_parts [M][slices][2] f32 with slices = rga3_gemm_lnsum_slices(N, tile) -- for row r and tile column
 // t, (sum, sum of squares) of the bf16 values this launch wrote to columns of that tile.  Plain stores, every element written once: nothing to zero, bitwise
-// reproducible.  bf16 output, no activation (proj / fc2 have none), tiles 3 / 5 / 12 / 13 / 20 / 23 (kernels of their own: LNM = 2).  Consumer: rga3_gemm_lnq_bf16.
-static int lnsum_tile_width(int tile) { return (tile == 3 || tile == 20) ? 256 : (tile == 5 || tile == 23) ? 192 : (tile == 13) ? 64 : 128; }
+// reproducible.  bf16 output, no activation (proj / fc2 have none), E_LNSUM tiles (kernels of their own: LNF = 2).  Consumer: rga3_gemm_lnq_bf16.
 extern "C" int64_t rga3_gemm_lnsum_slices(int64_t N, int tile) {
-    if (N <= 0 || !(tile == -1 || tile == 3 || tile == 5 || tile == 12 || tile == 13 || tile == 20 || tile == 23)) return -1;
-    return cdiv(N, lnsum_tile_width(tile));
+    const Tile* t = find_tile(tile, E_LNSUM);
+    return (N > 0 && t) ? cdiv(N, t->bn) : -1;
 }
 extern "C" int rga3_gemm_lnsum_bf16(const void* A, const void* W, const void* bias, const void* residual, void* C, int64_t M, int64_t N, int64_t K, int64_t lda,
                                     int64_t ldw, int64_t ldc, int64_t ldr, int tile, float* row_parts, void* stream) {
-    RGA3_CHECK_ARG(A && W && C && row_parts && (((uintptr_t)row_parts) & 7) == 0, "gemm_lnsum: null pointer / row_parts must be 8-byte aligned");
+    RGA3_CHECK_ARG(row_parts && (((uintptr_t)row_parts) & 7) == 0, "gemm_lnsum: null pointer / row_parts must be 8-byte aligned");
     RGA3_CHECK_ARG(M > 16 && N > 0 && K > 0 && K % 8 == 0, "gemm_lnsum: bad shape M=%ld N=%ld K=%ld (M > 16, K %% 8)", (long)M, (long)N, (long)K);
-    RGA3_CHECK_ARG(lda % 8 == 0 && ldw % 8 == 0, "gemm_lnsum: lda/ldw must be multiples of 8 elements (16-byte rows)");
-    RGA3_CHECK_ARG((((uintptr_t)A | (uintptr_t)W | (uintptr_t)C) & 15) == 0, "gemm_lnsum: pointers must be 16-byte aligned");
-    RGA3_CHECK_ARG(tile == -1 || tile == 3 || tile == 5 || tile == 12 || tile == 13 || tile == 20 || tile == 23, "gemm_lnsum: tile %d (3 / 5 / 12 / 13 / 20 / 23)", tile);
-    RGA3_CHECK_ARG(M * lda < (1LL << 32) && N * ldw < (1LL << 32), "gemm_lnsum: operands must be < 2^32 elements (32-bit staging offsets)");
+    const Tile* t = find_tile(tile, E_LNSUM);
+    RGA3_CHECK_ARG(t, "gemm_lnsum: tile %d", tile);
     GemmArgs a;
-    a.A = (const unsigned short*)A; a.W = (const unsigned short*)W; a.C = C;
-    a.bias = (const unsigned short*)bias; a.res = (const unsigned short*)residual; a.colscale = nullptr;
-    a.M = (int)M; a.N = (int)N; a.K = (int)K;
-    a.lda = lda; a.ldw = ldw; a.ldc = ldc; a.ldr = ldr;
-    a.ws = nullptr; a.ws_bytes = 0; a.ksl = 0; a.rowstat = nullptr; a.colc = nullptr;
+    if (int rc = nt_args(a, "gemm_lnsum", A, W, bias, residual, C, M, N, K, lda, ldw, ldc, ldr)) return rc;
     a.ln_parts = row_parts;
-    hipStream_t st = (hipStream_t)stream;
-    switch (tile) {
-        case 3: return launch_cfg<128, 256, 2, 4, ACT_NONE, false, 0, 2>(a, st);
-        case 5: return launch_cfg<128, 192, 2, 4, ACT_NONE, false, 0, 2>(a, st);
-        case 13: return launch_cfg<64, 64, 2, 2, ACT_NONE, false, 0, 2>(a, st);
-        case 20: return launch_pp<ACT_NONE, false, 2, false>(a, st);
-        case 23: return launch_pp<ACT_NONE, false, 2, true>(a, st);
-        default: return launch_cfg<128, 128, 2, 2, ACT_NONE, false, 0, 2>(a, st);
-    }
+    return launch_tile<ACT_NONE, false, 2>(a, t->id, (hipStream_t)stream);
 }
 
 // SwiGLU product that ALSO stores its bf16 pre-activations (training forward of the decoder MLP: the backward of silu(gate) * up needs gate and up; HF Qwen2MLP,
@@ -2888,143 +3018,65 @@ extern "C" int rga3_gemm_swiglu_pre_bf16(const void* A, const void* W, const voi
 // train_joint.py:193-232):
 //   K side (A2, W2, K2 != 0):  C [M, N] = [A | A2] . [W | W2]^T (+ bias): y = x W^T + t B^T as ONE product over K + K2 (K, K2 multiples of 64)
 //   N side (Wn, Cn, N2 != 0):  additionally Cn [M, N2] = A . Wn^T from the same launch (tile columns behind N; N must be a multiple of the tile width): [dx | dt] = dy [W | sB]
-// bf16 in / out, no activation, optional bias on the first pair.  tile: -1 / 12 (128 x 128), 3 (128 x 256), 6 (128 x 256, three stages), 13 (64 x 64); K side only: also 4, 5.
+// bf16 in / out, no activation, optional bias on the first pair.  Tiles: E_CATN with an N side, else E_CATK.
 extern "C" int rga3_gemm_cat_bf16(const void* A, const void* W, const void* bias, void* C, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldw, int64_t ldc,
                                   const void* A2, const void* W2, int64_t K2, int64_t lda2, int64_t ldw2, const void* Wn, void* Cn, int64_t N2, int64_t ldwn,
                                   int64_t ldcn, int tile, void* stream) {
-    RGA3_CHECK_ARG(A && W && C && M > 16 && N > 0 && K > 0, "gemm_cat: bad args");
+    RGA3_CHECK_ARG(M > 16 && N > 0 && K > 0, "gemm_cat: bad args");
     RGA3_CHECK_ARG((A2 != nullptr) == (W2 != nullptr) && (A2 != nullptr) == (K2 > 0), "gemm_cat: the K side takes A2, W2 and K2 together");
     RGA3_CHECK_ARG((Wn != nullptr) == (Cn != nullptr) && (Wn != nullptr) == (N2 > 0), "gemm_cat: the N side takes Wn, Cn and N2 together");
     RGA3_CHECK_ARG(A2 || Wn, "gemm_cat: nothing concatenated (use rga3_gemm_bf16)");
     RGA3_CHECK_ARG(K % 64 == 0 && K2 % 64 == 0, "gemm_cat: K = %ld and K2 = %ld must be multiples of 64", (long)K, (long)K2);
-    RGA3_CHECK_ARG(lda % 8 == 0 && ldw % 8 == 0 && lda2 % 8 == 0 && ldw2 % 8 == 0 && ldwn % 8 == 0 && N % 8 == 0 && N2 % 8 == 0, "gemm_cat: strides / widths must be multiples of 8 elements");
-    RGA3_CHECK_ARG((((uintptr_t)A | (uintptr_t)W | (uintptr_t)C | (uintptr_t)A2 | (uintptr_t)W2 | (uintptr_t)Wn | (uintptr_t)Cn) & 15) == 0, "gemm_cat: pointer alignment");
-    RGA3_CHECK_ARG(M * lda < (1LL << 32) && N * ldw < (1LL << 32) && M * (lda2 ? lda2 : 1) < (1LL << 32) && N * (ldw2 ? ldw2 : 1) < (1LL << 32) && N2 * (ldwn ? ldwn : 1) < (1LL << 32),
-                   "gemm_cat: operands must be < 2^32 elements");
-    const int bn = (tile == 3 || tile == 6) ? 256 : (tile == 4) ? 320 : (tile == 5) ? 192 : (tile == 13) ? 64 : 128;
-    RGA3_CHECK_ARG(tile == -1 || tile == 3 || tile == 6 || tile == 12 || tile == 13 || (!Wn && (tile == 4 || tile == 5)), "gemm_cat: tile %d", tile);
-    RGA3_CHECK_ARG(!Wn || N % bn == 0, "gemm_cat: with an N side, N = %ld must be a multiple of the tile width %d", (long)N, bn);
+    RGA3_CHECK_ARG(lda2 % 8 == 0 && ldw2 % 8 == 0 && ldwn % 8 == 0 && N % 8 == 0 && N2 % 8 == 0, "gemm_cat: strides / widths must be multiples of 8 elements");
+    RGA3_CHECK_ARG((((uintptr_t)A2 | (uintptr_t)W2 | (uintptr_t)Wn | (uintptr_t)Cn) & 15) == 0, "gemm_cat: pointer alignment");
+    RGA3_CHECK_ARG(M * (lda2 ? lda2 : 1) < (1LL << 32) && N * (ldw2 ? ldw2 : 1) < (1LL << 32) && N2 * (ldwn ? ldwn : 1) < (1LL << 32), "gemm_cat: operands must be < 2^32 elements");
+    const Tile* t = find_tile(tile, Wn ? E_CATN : E_CATK);
+    RGA3_CHECK_ARG(t, "gemm_cat: tile %d", tile);
+    RGA3_CHECK_ARG(!Wn || N % t->bn == 0, "gemm_cat: with an N side, N = %ld must be a multiple of the tile width %d", (long)N, t->bn);
     GemmArgs a;
-    a.A = (const unsigned short*)A; a.W = (const unsigned short*)W; a.C = C;
-    a.bias = (const unsigned short*)bias; a.res = nullptr; a.colscale = nullptr;
-    a.M = (int)M; a.N = (int)N; a.K = (int)K;
-    a.lda = lda; a.ldw = ldw; a.ldc = ldc; a.ldr = 0;
-    a.ws = nullptr; a.ws_bytes = 0; a.ksl = 0; a.rowstat = nullptr; a.colc = nullptr;
+    if (int rc = nt_args(a, "gemm_cat", A, W, bias, nullptr, C, M, N, K, lda, ldw, ldc, 0)) return rc;
     a.A2 = (const unsigned short*)A2; a.W2 = (const unsigned short*)W2; a.K2 = (int)K2; a.lda2 = lda2; a.ldw2 = ldw2;
     a.Wn = (const unsigned short*)Wn; a.Cn = Cn; a.N2 = (int)N2; a.ldwn = ldwn; a.ldcn = ldcn;
-    hipStream_t st = (hipStream_t)stream;
-    switch (tile) {
-        case 3: return launch_cfg<128, 256, 2, 4, ACT_NONE, false, 0>(a, st);
-        case 4: return launch_cfg<128, 320, 2, 4, ACT_NONE, false, 0>(a, st);
-        case 5: return launch_cfg<128, 192, 2, 4, ACT_NONE, false, 0>(a, st);
-        case 6: return launch_cfg<128, 256, 2, 4, ACT_NONE, false, 3>(a, st);
-        case 13: return launch_cfg<64, 64, 2, 2, ACT_NONE, false, 0>(a, st);
-        default: return launch_cfg<128, 128, 2, 2, ACT_NONE, false, 0>(a, st);
-    }
-}
-
-static int gemm_bf16_impl(const void* A, const void* W, const void* bias, const void* residual, const void* colscale, void* C,
-                          int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldw, int64_t ldc, int64_t ldr,
-                          int act, int out_dtype, int tile, void* workspace, int64_t workspace_bytes, const unsigned long long* rs_in, int64_t rs_width, float rs_eps,
-                          unsigned long long* rs_out, void* stream, void* pre, int64_t ldpre) {
-    RGA3_CHECK_ARG(A && W && C, "gemm: null pointer");
-    RGA3_CHECK_ARG(!pre || (act == ACT_SWIGLU && M > 4 && tile != 40 && tile != 41 && (((uintptr_t)pre) & 15) == 0 && ldpre >= N), "gemm: the pre-activation output goes with the SwiGLU tile epilogues (M > 4)");
-    RGA3_CHECK_ARG(M > 0 && N > 0 && K > 0, "gemm: bad shape M=%ld N=%ld K=%ld", (long)M, (long)N, (long)K);
-    RGA3_CHECK_ARG(K % 8 == 0, "gemm: K=%ld must be a multiple of 8 (16-byte staging chunks)", (long)K);
-    RGA3_CHECK_ARG(lda % 8 == 0 && ldw % 8 == 0, "gemm: lda/ldw must be multiples of 8 elements (16-byte rows)");
-    RGA3_CHECK_ARG((((uintptr_t)A | (uintptr_t)W | (uintptr_t)C) & 15) == 0, "gemm: pointers must be 16-byte aligned");
-    RGA3_CHECK_ARG(out_dtype == RGA3_BF16 || out_dtype == RGA3_F32, "gemm: out_dtype %d", out_dtype);
-    RGA3_CHECK_ARG(act >= 0 && act <= 3, "gemm: act %d", act);
-    RGA3_CHECK_ARG(!(out_dtype == RGA3_F32 && (act != ACT_NONE || residual || colscale)), "gemm: f32 output supports bias only");
-    RGA3_CHECK_ARG(act != ACT_SWIGLU || N % 32 == 0, "gemm: swiglu needs N %% 32 == 0");
-    RGA3_CHECK_ARG(tile == -1 || (tile >= 3 && tile <= 8) || (tile >= 10 && tile <= 14) || (tile >= 20 && tile <= 23) || tile == 25 || (tile >= 26 && tile <= 28) || tile == 31 || tile == 32 || tile == 40 || tile == 41, "gemm: tile %d", tile);
-    RGA3_CHECK_ARG(M * lda < (1LL << 32) && N * ldw < (1LL << 32), "gemm: operands must be < 2^32 elements (32-bit staging offsets)");
-    GemmArgs a;
-    a.A = (const unsigned short*)A;
-    a.W = (const unsigned short*)W;
-    a.C = C;
-    a.bias = (const unsigned short*)bias;
-    a.res = (const unsigned short*)residual;
-    a.colscale = (const unsigned short*)colscale;
-    a.M = (int)M; a.N = (int)N; a.K = (int)K;
-    a.lda = lda; a.ldw = ldw; a.ldc = ldc; a.ldr = ldr;
-    a.ws = workspace; a.ws_bytes = workspace_bytes; a.ksl = 0; a.rowstat = nullptr; a.colc = nullptr;
-    a.rs_in = rs_in; a.rs_in_scale = rs_in ? 1.0f / (kRowSumFix * (float)rs_width) : 0.f; a.rs_eps = rs_eps; a.rs_out = rs_out;
-    a.pre = (unsigned short*)pre; a.ldpre = ldpre;
-    hipStream_t st = (hipStream_t)stream;
-    RGA3_CHECK_ARG(tile != 40 || (M <= 4 && !colscale), "gemm: the skinny kernel (tile 40) takes M <= 4 rows and no column scale");
-    const bool rows16_ok = M <= 16 && !colscale && out_dtype == RGA3_BF16 && act != ACT_SWIGLU;
-    RGA3_CHECK_ARG(tile != 41 || rows16_ok, "gemm: the token-row kernel (tile 41) takes M <= 16 rows, bf16 output, no column scale, no SwiGLU");
-    int tl = (tile == -1 && M <= 4 && !colscale) ? 40 : (tile == -1 && rows16_ok) ? 41 : pick_tile((int)M, (int)N, (int)K, act == ACT_NONE && !residual && !colscale && !rs_in && !rs_out, tile);   // row sums live in the shared epilogue: never the split-K tile
-    if (out_dtype == RGA3_F32) return launch_act<ACT_NONE, true>(a, tl, st);
-    switch (act) {
-        case ACT_NONE: return launch_act<ACT_NONE, false>(a, tl, st);
-        case ACT_GELU: return launch_act<ACT_GELU, false>(a, tl, st);
-        case ACT_SWIGLU: return launch_act<ACT_SWIGLU, false>(a, tl, st);
-        default: return launch_act<ACT_RELU, false>(a, tl, st);
-    }
-}
-
-template <int ACT>
-static int launch_ln(const GemmArgs& a, int tile, hipStream_t st) {
-    switch (tile) {
-        case 3: return launch_cfg<128, 256, 2, 4, ACT, false, 0, true>(a, st);
-        case 5: return launch_cfg<128, 192, 2, 4, ACT, false, 0, true>(a, st);
-        case 6: return launch_cfg<128, 256, 2, 4, ACT, false, 3, true>(a, st);
-        case 7: return launch_cfg<128, 192, 2, 4, ACT, false, 3, true>(a, st);
-        case 13: return launch_cfg<64, 64, 2, 2, ACT, false, 0, true>(a, st);
-        case 20: return launch_pp<ACT, false, true>(a, st);
-        default: return launch_cfg<128, 128, 2, 2, ACT, false, 0, true>(a, st);
-    }
+    return launch_tile<ACT_NONE, false, 0>(a, t->id, (hipStream_t)stream);
 }
 
 // C[M, N] (bf16) = act(LayerNorm(A) . W^T + b) with the LayerNorm folded into the product (see gemm_epilogue, LNF): A [M, K] un-normalised rows, Wf [N, K] the
-// weight with gamma folded in, colc [N] f32 column sums of Wf, bias [N] bf16 = beta . W^T + b, rowstat [M][2] f32 from rga3_layernorm_stats.
-// act: none / gelu / relu.  tile: -1 (128 x 128) or 3 / 5 / 12 / 13 / 20.
+// weight with gamma folded in, colc [N] f32 column sums of Wf, bias [N] bf16 = beta . W^T + b.  The row statistics come either as rowstat [M][2] f32 = (mean, 1 / std)
+// from rga3_layernorm_stats (rga3_gemm_ln_bf16), or as the producer's partial sums (rga3_gemm_lnsum_bf16) row_parts [M][slices][2] f32 with norm_width = the width the
+// sums were taken over (= K here) and the LayerNorm's eps (rga3_gemm_lnq_bf16): mean = S1 / w, var = S2 / w - mean^2 (f64 inside the kernel), biased variance as
+// nn.LayerNorm.  act: none / gelu / relu.  Tiles: E_LN.  `who` = the entry point's message prefix; stats = rowstat or row_parts (8-byte aligned).
+static int gemm_ln_args(GemmArgs& a, const char* who, const void* A, const void* Wf, const void* bias, const float* colc, const float* stats, void* C, int64_t M, int64_t N,
+                        int64_t K, int64_t lda, int64_t ldw, int64_t ldc, int act, int tile) {
+    RGA3_CHECK_ARG(colc && stats, "%s: null pointer", who);
+    RGA3_CHECK_ARG(M > 0 && N > 0 && K > 0 && K % 8 == 0 && N % 4 == 0, "%s: bad shape M=%ld N=%ld K=%ld (K %% 8, N %% 4)", who, (long)M, (long)N, (long)K);
+    RGA3_CHECK_ARG((((uintptr_t)colc) & 15) == 0 && (((uintptr_t)stats) & 7) == 0, "%s: pointer alignment", who);
+    RGA3_CHECK_ARG(act == ACT_NONE || act == ACT_GELU || act == ACT_RELU, "%s: act %d", who, act);
+    RGA3_CHECK_ARG(find_tile(tile, E_LN), "%s: tile %d", who, tile);
+    if (int rc = nt_args(a, who, A, Wf, bias, nullptr, C, M, N, K, lda, ldw, ldc, 0)) return rc;
+    a.colc = colc;
+    return 0;
+}
+static int launch_ln(const GemmArgs& a, int act, int tile, void* stream) {
+    const int id = find_tile(tile, E_LN)->id;
+    hipStream_t st = (hipStream_t)stream;
+    if (act == ACT_GELU) return launch_tile<ACT_GELU, false, 1>(a, id, st);
+    if (act == ACT_RELU) return launch_tile<ACT_RELU, false, 1>(a, id, st);
+    return launch_tile<ACT_NONE, false, 1>(a, id, st);
+}
 extern "C" int rga3_gemm_ln_bf16(const void* A, const void* Wf, const void* bias, const float* colc, const float* rowstat, void* C, int64_t M, int64_t N, int64_t K,
                                  int64_t lda, int64_t ldw, int64_t ldc, int act, int tile, void* stream) {
-    RGA3_CHECK_ARG(A && Wf && C && colc && rowstat, "gemm_ln: null pointer");
-    RGA3_CHECK_ARG(M > 0 && N > 0 && K > 0 && K % 8 == 0 && N % 4 == 0, "gemm_ln: bad shape M=%ld N=%ld K=%ld (K %% 8, N %% 4)", (long)M, (long)N, (long)K);
-    RGA3_CHECK_ARG(lda % 8 == 0 && ldw % 8 == 0, "gemm_ln: lda/ldw must be multiples of 8 elements");
-    RGA3_CHECK_ARG((((uintptr_t)A | (uintptr_t)Wf | (uintptr_t)C | (uintptr_t)colc) & 15) == 0 && (((uintptr_t)rowstat) & 7) == 0, "gemm_ln: pointer alignment");
-    RGA3_CHECK_ARG(act == ACT_NONE || act == ACT_GELU || act == ACT_RELU, "gemm_ln: act %d", act);
-    RGA3_CHECK_ARG(tile == -1 || tile == 3 || (tile >= 5 && tile <= 7) || tile == 12 || tile == 13 || tile == 20, "gemm_ln: tile %d", tile);
-    RGA3_CHECK_ARG(M * lda < (1LL << 32) && N * ldw < (1LL << 32), "gemm_ln: operands must be < 2^32 elements");
     GemmArgs a;
-    a.A = (const unsigned short*)A; a.W = (const unsigned short*)Wf; a.C = C;
-    a.bias = (const unsigned short*)bias; a.res = nullptr; a.colscale = nullptr;
-    a.M = (int)M; a.N = (int)N; a.K = (int)K;
-    a.lda = lda; a.ldw = ldw; a.ldc = ldc; a.ldr = 0;
-    a.ws = nullptr; a.ws_bytes = 0; a.ksl = 0; a.rowstat = rowstat; a.colc = colc;
-    hipStream_t st = (hipStream_t)stream;
-    if (act == ACT_GELU) return launch_ln<ACT_GELU>(a, tile, st);
-    if (act == ACT_RELU) return launch_ln<ACT_RELU>(a, tile, st);
-    return launch_ln<ACT_NONE>(a, tile, st);
+    if (int rc = gemm_ln_args(a, "gemm_ln", A, Wf, bias, colc, rowstat, C, M, N, K, lda, ldw, ldc, act, tile)) return rc;
+    a.rowstat = rowstat;
+    return launch_ln(a, act, tile, stream);
 }
-
-// rga3_gemm_ln_bf16 reading the statistics as the producer's partial sums (rga3_gemm_lnsum_bf16) instead of (mean, 1 / std): row_parts [M][slices][2] f32, norm_width
-// = the width the sums were taken over (= K here), eps the LayerNorm's.  mean = S1 / w, var = S2 / w - mean^2 (f64 inside the kernel), biased variance as nn.LayerNorm.
 extern "C" int rga3_gemm_lnq_bf16(const void* A, const void* Wf, const void* bias, const float* colc, const float* row_parts, int64_t slices, int64_t norm_width,
                                   float eps, void* C, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldw, int64_t ldc, int act, int tile, void* stream) {
-    RGA3_CHECK_ARG(A && Wf && C && colc && row_parts, "gemm_lnq: null pointer");
-    RGA3_CHECK_ARG(M > 0 && N > 0 && K > 0 && K % 8 == 0 && N % 4 == 0 && norm_width > 0 && eps >= 0.f && slices >= 1 && slices <= 4096,
-                   "gemm_lnq: bad shape M=%ld N=%ld K=%ld slices=%ld (K %% 8, N %% 4)", (long)M, (long)N, (long)K, (long)slices);
-    RGA3_CHECK_ARG(lda % 8 == 0 && ldw % 8 == 0, "gemm_lnq: lda/ldw must be multiples of 8 elements");
-    RGA3_CHECK_ARG((((uintptr_t)A | (uintptr_t)Wf | (uintptr_t)C | (uintptr_t)colc) & 15) == 0 && (((uintptr_t)row_parts) & 7) == 0, "gemm_lnq: pointer alignment");
-    RGA3_CHECK_ARG(act == ACT_NONE || act == ACT_GELU || act == ACT_RELU, "gemm_lnq: act %d", act);
-    RGA3_CHECK_ARG(tile == -1 || tile == 3 || (tile >= 5 && tile <= 7) || tile == 12 || tile == 13 || tile == 20, "gemm_lnq: tile %d", tile);
-    RGA3_CHECK_ARG(M * lda < (1LL << 32) && N * ldw < (1LL << 32), "gemm_lnq: operands must be < 2^32 elements");
+    RGA3_CHECK_ARG(norm_width > 0 && eps >= 0.f && slices >= 1 && slices <= 4096, "gemm_lnq: bad norm_width=%ld eps=%g slices=%ld", (long)norm_width, (double)eps, (long)slices);
     GemmArgs a;
-    a.A = (const unsigned short*)A; a.W = (const unsigned short*)Wf; a.C = C;
-    a.bias = (const unsigned short*)bias; a.res = nullptr; a.colscale = nullptr;
-    a.M = (int)M; a.N = (int)N; a.K = (int)K;
-    a.lda = lda; a.ldw = ldw; a.ldc = ldc; a.ldr = 0;
-    a.ws = nullptr; a.ws_bytes = 0; a.ksl = 0; a.rowstat = nullptr; a.colc = colc;
+    if (int rc = gemm_ln_args(a, "gemm_lnq", A, Wf, bias, colc, row_parts, C, M, N, K, lda, ldw, ldc, act, tile)) return rc;
     a.ln_in = row_parts; a.ln_ns = (int)slices; a.rs_in_scale = 1.0f / (float)norm_width; a.rs_eps = eps;
-    hipStream_t st = (hipStream_t)stream;
-    if (act == ACT_GELU) return launch_ln<ACT_GELU>(a, tile, st);
-    if (act == ACT_RELU) return launch_ln<ACT_RELU>(a, tile, st);
-    return launch_ln<ACT_NONE>(a, tile, st);
+    return launch_ln(a, act, tile, stream);
 }
 
 // C[M, N] (bf16 or f32) = A^T . B (+ bias[n]) with A [K, M], B [K, N] bf16 row-major: the weight-gradient product dW = dY^T X without
@@ -3048,18 +3100,8 @@ extern "C" int rga3_gemm_tn_bf16(const void* A, const void* B, const void* bias,
     t.A = (const unsigned short*)A; t.B = (const unsigned short*)B; t.lda = lda; t.ldb = ldb; t.K = (int)K;
     t.counters = nullptr; t.out = nullptr; t.ldo = 0; t.out_f32 = 0;
     const int nk = (int)cdiv(K, 32);
-    // few output tiles over many tokens (LoRA dW: 1 x 28 tiles, K = 2112 / 4160; mask-path dW: 1-4 tiles, K = 65 536 ..): cut K into Z slices, one workgroup each, f32 partial slabs in
-    // the caller's workspace, summed in fixed order by a second launch (deterministic; no atomics)
-    int Z = 1;
     const long tiles = (long)a.ntm * a.ntn;
-    if (workspace && !bias && tiles < 128 && nk >= 32) {
-        Z = (int)(256 / tiles);
-        if (Z > 64) Z = 64;   // (16 until round 2: per-pixel weight gradients of the mask path, 1-4 tiles over 65 536 - 262 144 rows, filled 64 CUs)
-        if (Z > nk / 8) Z = nk / 8;
-        const long fit = workspace_bytes / (M * N * 4);
-        if (Z > fit) Z = (int)fit;
-        if (Z < 2) Z = 1;
-    }
+    int Z = (workspace && !bias) ? tn_slices(M, N, K, workspace_bytes) : 1;   // the slabs live in the caller's workspace; the slab sum adds no bias
     hipStream_t st = (hipStream_t)stream;
     if (Z == 1) {
         t.kt_per_z = nk; t.slab = 0;
@@ -3121,13 +3163,7 @@ extern "C" int rga3_gemm_tn_many(const void* const* ptrs, const int64_t* dims, i
         t.counters = nullptr; t.out = nullptr; t.ldo = 0; t.out_f32 = 0;
         const int nk = (int)cdiv(K, 32);
         const long tiles = (long)a.ntm * a.ntn;
-        int Z = 1;
-        if (tiles < 128 && nk >= 32) {     // the single form's rule
-            Z = (int)(256 / tiles);
-            if (Z > 64) Z = 64;
-            if (Z > nk / 8) Z = nk / 8;
-            if (Z < 2) Z = 1;
-        }
+        int Z = tn_slices(M, N, K, INT64_MAX);   // the slices of the single form with room for all of them: a short workspace is an error below
         t.kt_per_z = (int)cdiv(nk, Z);
         Z = (int)cdiv(nk, t.kt_per_z);
         t.slab = M * N;

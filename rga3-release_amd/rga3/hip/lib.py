@@ -73,6 +73,7 @@ SIGNATURES = {
     "rga3_gemm_stream_k_timeouts": [_p],
     "rga3_gemm_timeout_counter_offset": [],
     "rga3_gemm_ragged_plan": [_i64, _i64, _i64, _i, _i, _p, _p],
+    "rga3_gemm_tiles": [_i, _p, _p, _p, _i],
     "rga3_quant_fp8_rows": [_p, _p, _p, _i64, _i64, _i64, _i64, _p],
     "rga3_gemm_fp8": [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _p],
     "rga3_swiglu_fwd_quant_fp8": [_p, _p, _p, _i64, _i64, _p],
@@ -149,6 +150,22 @@ def last_error() -> str:
     buf = C.create_string_buffer(512)
     load().rga3_last_error(buf, 512)
     return buf.value.decode("utf-8", "replace")
+
+
+_TILE_ENTRIES = ("plain", "shared", "ln", "lnsum", "cat_k", "cat_n")
+_tiles = {}
+
+
+def gemm_tiles(entry: str) -> dict:
+    """{tile id: tile width} of the tilings a bf16 GEMM entry point has kernels for, in the order the tuner is to try them.  Read once from the library's own
+    table (rga3_gemm_tiles: host only, no device call) -- the table the entry points check their ``tile`` argument against."""
+    if entry not in _tiles:
+        ids, bm, bn = ((C.c_int * 64)() for _ in range(3))
+        n = load().rga3_gemm_tiles(_TILE_ENTRIES.index(entry), ids, bm, bn, 64)
+        if not 0 < n <= 64:
+            raise Rga3Error("rga3_gemm_tiles failed: " + last_error())
+        _tiles[entry] = {ids[i]: bn[i] for i in range(n)}
+    return _tiles[entry]
 
 
 def check(rc: int, what: str):

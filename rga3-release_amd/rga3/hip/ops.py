@@ -90,9 +90,6 @@ def gemm_stream_k_timeouts(device=None) -> int:
     return tot
 
 
-_LNSUM_TILES = (20, 3, 5, 12, 13, 23)      # the tilings rga3_gemm_lnsum_bf16 has kernels for
-
-
 def gemm(a: torch.Tensor, w: torch.Tensor, bias=None, residual=None, act: str = "none", out_dtype=torch.bfloat16,
          out=None, tile: int = -1, colscale=None, rms_in=None, rms_out=None) -> torch.Tensor:
     """out = residual + colscale * act(a @ w.T + bias).  a [M,K], w [N,K] (nn.Linear layout), bf16.
@@ -151,7 +148,7 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias=None, residual=None, act: str = 
     if rms:
         if tile == -1:
             tile = _tuner.pick(_tuner.key_of(M, N, K, act, odt, bias is not None, residual is not None), lambda t: run(t, final=False))
-            if tile in (14, 25, 40, 41):     # decided for the plain product of the same shape: those tilings have their own epilogues
+            if tile not in _lib.gemm_tiles("shared"):     # decided for the plain product of the same shape: those tilings have their own epilogues
                 tile = -1
         run(tile)
         return out
@@ -191,7 +188,7 @@ def gemm_swiglu_pre(a, w, bias=None, tile: int = -1):
 
     if tile == -1 and M * N * K >= (1 << 24):
         tile = _tuner.pick(_tuner.key_of(M, N, K, "swiglu+pre", BF16, bias is not None, False), run)
-        if tile in (14, 25, 40, 41):    # forced (tuner.force) tilings with an epilogue of their own: no pre-activation store there
+        if tile not in _lib.gemm_tiles("shared"):    # forced (tuner.force) tilings with an epilogue of their own: no pre-activation store there
             tile = -1
     run(tile)
     return out, pre
@@ -224,7 +221,7 @@ def gemm_cat(a, w, bias=None, a2=None, w2=None, wn=None, tile: int = -1):
                       out_n.stride(0) if out_n is not None else 0, t, _stream()), "gemm_cat_bf16")
 
     if tile == -1:
-        cands = tuple(t for t in ((12, 3, 6, 13) if wn is not None else (12, 3, 4, 5, 6, 13)) if wn is None or N % (256 if t in (3, 6) else 64 if t == 13 else 128) == 0)
+        cands = tuple(t for t, bn in _lib.gemm_tiles("cat_k" if wn is None else "cat_n").items() if wn is None or N % bn == 0)
         tile = _tuner.pick(_tuner.key_of(M, N + N2, K + K2, "cat", BF16, bias is not None, False), run, candidates=cands)
         if tile not in cands:    # a tiling forced for the plain GEMMs (tuner.force) that this entry point does not have
             tile = -1
@@ -320,9 +317,6 @@ def hiera_mlp(x, wf, colc, biasf, w2, b2, eps: float):
 hiera_mlp144 = hiera_mlp      # the round-3 name (stage 1 only)
 
 
-_LN_TILES = (20, 3, 5, 12, 13, 6, 7)     # (6 / 7: the three-stage 128 x 256 / 128 x 192 forms -- two K-tiles in flight; offered to the tuner since round 6)
-
-
 class LnSums:
     """Row statistics as the PRODUCER's partial sums: t [M, slices, 2] f32 = (sum x, sum x^2) per row and tile column of the product that wrote the rows
     (gemm_lnsum), eps of the LayerNorm that will consume them.  gemm_ln takes it in place of layernorm_stats' (mean, 1 / std)."""
@@ -353,9 +347,9 @@ def gemm_lnsum(a, w, bias=None, residual=None, tile: int = -1):
             _lib.check(L.rga3_gemm_bf16(a.data_ptr(), w.data_ptr(), _ptr(bias), _ptr(residual), None, out.data_ptr(), M, N, K, a.stride(0), w.stride(0), out.stride(0), ldr,
                                         ACT["none"], BF16, t, ws.data_ptr(), ws.numel(), _stream()), "gemm_bf16")
 
-        cands = _LNSUM_TILES if (N % 192 == 0 and N % 256 != 0 and M >= 1024) else tuple(t for t in _LNSUM_TILES if t != 23)
+        cands = tuple(t for t in _lib.gemm_tiles("lnsum") if t != 23 or (N % 192 == 0 and N % 256 != 0 and M >= 1024))
         tile = _tuner.pick(_tuner.key_of(M, N, K, "lnsum", BF16, bias is not None, residual is not None), trial, candidates=cands)
-    if tile not in _LNSUM_TILES:
+    if tile not in _lib.gemm_tiles("lnsum"):
         tile = -1
     ns = int(L.rga3_gemm_lnsum_slices(N, tile))
     if ns < 1:
@@ -394,8 +388,8 @@ def gemm_ln(a, stats, wf, colc, biasf, act: str = "none", out=None, tile: int = 
                           ACT[act], t, _stream()), "gemm_ln_bf16")
 
     if tile == -1 and M * N * K >= (1 << 24):
-        tile = _tuner.pick(_tuner.key_of(M, N, K, "ln+" + act, BF16, biasf is not None, False), run, candidates=_LN_TILES)
-        if tile not in _LN_TILES:    # a tiling forced for the plain GEMMs (tuner.force) that this entry point does not have
+        tile = _tuner.pick(_tuner.key_of(M, N, K, "ln+" + act, BF16, biasf is not None, False), run, candidates=tuple(_lib.gemm_tiles("ln")))
+        if tile not in _lib.gemm_tiles("ln"):    # a tiling forced for the plain GEMMs (tuner.force) that this entry point does not have
             tile = -1
     run(tile)
     return out
