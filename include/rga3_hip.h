@@ -268,6 +268,16 @@ int rga3_bce_dice_sums(const float* logits, const float* targets, float* out4, i
 /* the same sums, reproducible run to run (per-block partial sums in `ws`, rga3_bce_dice_sums_ws_floats() f32 elements, added in block order; no atomics) */
 int64_t rga3_bce_dice_sums_ws_floats(int64_t n_masks, int64_t hw);
 int rga3_bce_dice_sums_det(const float* logits, const float* targets, float* out4, float* ws, int64_t ws_floats, int64_t n_masks, int64_t hw, void* stream);
+/* The integer counts behind the J&F score every video benchmark of the reference reports (csrc/maskmetrics.hip), for reference evaluation/mevis_val_u/eval_mevis.py:48-49
+ * (db_eval_iou / db_eval_boundary per sequence) and evaluation/revos/metrics.py:43-74, 94-214 (db_eval_iou, f_measure, _seg2bmap; the reference dilates with OpenCV on
+ * the host).  seg (prediction), ann (ground truth), void_pixels (optional, NULL = none): contiguous [frames, h, w] arrays of 1-byte elements, nonzero = set; both
+ * masks are ANDed with ~void.  counts int64 [frames, 6] = {n_fg, n_gt, fg_match, gt_match, inter, union} per frame: boundary pixels of seg / of ann (_seg2bmap), those
+ * of seg within `radius` of a boundary pixel of ann (|b_seg & dilate(b_ann, disk(radius))|, disk = {dx^2 + dy^2 <= radius^2}, nothing outside the frame contributes)
+ * and the other way round, |seg & ann|, |seg | ann|.  1 <= radius <= 64, frames <= 65535.  ws: rga3_mask_jf_ws_bytes(frames, h, w) bytes of caller workspace, 8-byte
+ * aligned (the two bit-packed boundary maps; < 0 = bad shape).  Exact integers (order-independent integer atomics); two launches on `stream`, no host round trip. */
+int64_t rga3_mask_jf_ws_bytes(int64_t frames, int64_t h, int64_t w);
+int rga3_mask_jf_counts(const void* seg, const void* ann, const void* void_pixels, int64_t* counts, void* ws, int64_t ws_bytes, int64_t frames, int64_t h, int64_t w,
+                        int radius, void* stream);
 
 /* ---- training step (backward + optimiser) ---------------------------------------------------------------- */
 

@@ -5,6 +5,8 @@ on ``torch.cuda.current_stream()`` and raises if the extension is missing or rej
 """
 from __future__ import annotations
 
+import math
+
 import torch
 
 from . import lib as _lib
@@ -959,6 +961,36 @@ def bce_dice_sums(logits, targets):
     nws = int(L.rga3_bce_dice_sums_ws_floats(n, hw))
     ws = torch.empty(nws, dtype=torch.float32, device=logits.device)
     _lib.check(L.rga3_bce_dice_sums_det(logits.data_ptr(), targets.data_ptr(), out.data_ptr(), ws.data_ptr(), nws, n, hw, _stream()), "bce_dice_sums_det")   # reproducible sums
+    return out
+
+
+def mask_jf_counts(annotation, segmentation, void_pixels=None, radius=None):
+    """Ground-truth / predicted (/ void) masks [T, h, w] or [h, w], bool or uint8 (nonzero = set) -> int64 [T, 6] (T = 1 for 2-D input) =
+    {n_fg, n_gt, fg_match, gt_match, inter, union} per frame: the counts of the reference's f_measure and db_eval_iou (evaluation/revos/metrics.py:43-74, 94-155),
+    boundary matches within ``radius`` pixels (1..64; None: the reference's default ceil(0.008 * hypot(h, w))).  Stays on the device: no synchronisation."""
+    _need_cuda(annotation, segmentation, void_pixels)
+    ts = [t for t in (segmentation, annotation, void_pixels) if t is not None]
+    for t in ts:
+        if t.dtype not in (torch.bool, torch.uint8):
+            raise _lib.Rga3Error(f"mask_jf_counts: masks are bool or uint8, got {t.dtype}")
+        if t.shape != annotation.shape or t.device != annotation.device:
+            raise _lib.Rga3Error(f"mask_jf_counts: shapes / devices differ: {tuple(t.shape)} on {t.device} vs {tuple(annotation.shape)} on {annotation.device}")
+    if annotation.dim() not in (2, 3):
+        raise _lib.Rga3Error(f"mask_jf_counts: [T, h, w] or [h, w] masks, got {tuple(annotation.shape)}")
+    h, w = annotation.shape[-2:]
+    T = annotation.shape[0] if annotation.dim() == 3 else 1
+    if radius is None:
+        radius = math.ceil(0.008 * math.hypot(h, w))
+    if int(radius) != radius:
+        raise _lib.Rga3Error(f"mask_jf_counts: radius {radius} is not an integer")
+    L = _lib.load()
+    nws = int(L.rga3_mask_jf_ws_bytes(T, h, w))
+    if nws < 0:
+        raise _lib.Rga3Error("mask_jf_ws_bytes failed: " + _lib.last_error())
+    seg, ann, vd = (None if t is None else t.contiguous() for t in (segmentation, annotation, void_pixels))
+    out = torch.empty((T, 6), dtype=torch.int64, device=ann.device)
+    ws = torch.empty(nws, dtype=torch.uint8, device=ann.device)
+    _lib.check(L.rga3_mask_jf_counts(seg.data_ptr(), ann.data_ptr(), _ptr(vd), out.data_ptr(), ws.data_ptr(), nws, T, h, w, int(radius), _stream()), "mask_jf_counts")
     return out
 
 
