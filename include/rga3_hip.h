@@ -278,6 +278,24 @@ int rga3_bce_dice_sums_det(const float* logits, const float* targets, float* out
 int64_t rga3_mask_jf_ws_bytes(int64_t frames, int64_t h, int64_t w);
 int rga3_mask_jf_counts(const void* seg, const void* ann, const void* void_pixels, int64_t* counts, void* ws, int64_t ws_bytes, int64_t frames, int64_t h, int64_t w,
                         int radius, void* stream);
+/* STOM on the device (csrc/stom.hip): the stage of reference model/STOM.py:72-207 between the point tracker and the preprocessors, for a whole clip, no host round
+ * trip.  frames_u8 / out: contiguous uint8 [frames, h, w, 3] (out != frames_u8), overlay_rgba uint8 [h, w, 4], tracks f32 [frames, n_points, 2] (x, y; finite),
+ * visibility 1-byte [frames, n_points] (nonzero = visible), n_points <= 16384, frames <= 65535, h * w < 2^31 - 256.  Every result equals the numpy path of
+ * rga3/model/STOM.py byte for byte.
+ * rga3_stom_flow: mean_flow (:102-131) per frame -> records int32 [frames, 4] = {apply, bits of dx (f32), bits of dy (f32), kept points}; apply = 0 leaves the frame
+ * untouched (no visible point, fewer than n_points / 2 kept by the median / MAD filter, a non-finite magnitude, or the prompt's own frame).
+ * rga3_stom_shift_composite: shift_overlay + composite (:145-160) from those records; frame vip_frame_idx composites the overlay unshifted.
+ * rga3_stom_mask_composite: warp_point (:163-207) for mask-shaped prompts: raster of the visible points, closing with the structuring element given as `spans`
+ * (HOST array, uint8 [max(ksize, 1), 2] = first / last set column of each kernel row; anchor ksize / 2, ksize <= 128), centroid, filled circle given as `half_widths`
+ * (HOST array, uint8 [radius + 1], row |dy| covers |dx| <= half_widths[|dy|]; radius <= 128) in the colour of the overlay's first alpha > 0 pixel, alpha clamped to
+ * [96, 148].  ws: rga3_stom_ws_bytes(frames, h, w) bytes of caller workspace, 8-byte aligned (per-frame sums and two bit-packed masks; < 0 = bad shape). */
+int64_t rga3_stom_ws_bytes(int64_t frames, int64_t h, int64_t w);
+int rga3_stom_flow(const float* tracks, const void* visibility, int* records, int64_t frames, int64_t n_points, int vip_frame_idx, void* stream);
+int rga3_stom_shift_composite(const void* frames_u8, const void* overlay_rgba, const int* records, void* out, int64_t frames, int64_t h, int64_t w, int vip_frame_idx,
+                              void* stream);
+int rga3_stom_mask_composite(const void* frames_u8, const void* overlay_rgba, const float* tracks, const void* visibility, void* out, void* ws, int64_t ws_bytes,
+                             int64_t frames, int64_t h, int64_t w, int64_t n_points, int vip_frame_idx, const void* spans, int ksize, const void* half_widths,
+                             int radius, void* stream);
 
 /* ---- training step (backward + optimiser) ---------------------------------------------------------------- */
 

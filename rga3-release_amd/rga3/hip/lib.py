@@ -60,6 +60,10 @@ SIGNATURES = {
     "rga3_bce_dice_sums_det": [_p, _p, _p, _p, _i64, _i64, _i64, _p],
     "rga3_mask_jf_ws_bytes": [_i64, _i64, _i64],
     "rga3_mask_jf_counts": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i, _p],
+    "rga3_stom_ws_bytes": [_i64, _i64, _i64],
+    "rga3_stom_flow": [_p, _p, _p, _i64, _i64, _i, _p],
+    "rga3_stom_shift_composite": [_p, _p, _p, _p, _i64, _i64, _i64, _i, _p],
+    "rga3_stom_mask_composite": [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i, _p, _i, _p, _i, _p],
     "rga3_attn_varlen_bwd": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i64, _i, _i, _i, _p, _f, _i, _p, _i64, _p],
     "rga3_transpose16_many": [_p, _p, _i, _p],
     "rga3_hiera_mlp144": [_p, _p, _p, _p, _p, _p, _p, _i64, _f, _p],
@@ -113,7 +117,7 @@ SIGNATURES = {
     "rga3_bce_dice_grad_dev": [_p, _p, _p, _p, _i64, _i64, _p, _p, _p],
 }
 
-_INT64_RESULTS = ("rga3_gemm_lnsum_slices", "rga3_hiera_mlp288_pack_bytes", "rga3_gemm_workspace_bytes", "rga3_memattn_cross_ws_floats", "rga3_gemm_timeout_counter_offset", "rga3_layernorm_bwd_ws_floats", "rga3_colsum_ws_floats", "rga3_mask_product_bwd_ws_floats", "rga3_bce_dice_sums_ws_floats", "rga3_mask_jf_ws_bytes")
+_INT64_RESULTS = ("rga3_gemm_lnsum_slices", "rga3_hiera_mlp288_pack_bytes", "rga3_gemm_workspace_bytes", "rga3_memattn_cross_ws_floats", "rga3_gemm_timeout_counter_offset", "rga3_layernorm_bwd_ws_floats", "rga3_colsum_ws_floats", "rga3_mask_product_bwd_ws_floats", "rga3_bce_dice_sums_ws_floats", "rga3_mask_jf_ws_bytes", "rga3_stom_ws_bytes")
 
 _lib = None
 

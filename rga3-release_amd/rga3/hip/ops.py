@@ -994,6 +994,89 @@ def mask_jf_counts(annotation, segmentation, void_pixels=None, radius=None):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ STOM on the device (csrc/stom.hip)
+STOM_MAX_POINTS = 16384
+STOM_MAX_KERNEL = 128
+_stom_ws = {}
+
+
+def _stom_points(name, tracks, visibility, vip_frame_idx):
+    _need_cuda(tracks, visibility)
+    if tracks.dtype != torch.float32 or tracks.dim() != 3 or tracks.shape[2] != 2 or not tracks.is_contiguous():
+        raise _lib.Rga3Error(f"{name}: tracks are contiguous float32 [T, N, 2], got {tracks.dtype} {tuple(tracks.shape)}")
+    T, N = tracks.shape[:2]
+    if visibility.dtype not in (torch.bool, torch.uint8) or tuple(visibility.shape) != (T, N) or not visibility.is_contiguous() or visibility.device != tracks.device:
+        raise _lib.Rga3Error(f"{name}: visibility is contiguous bool [{T}, {N}] on {tracks.device}, got {visibility.dtype} {tuple(visibility.shape)} on {visibility.device}")
+    if not 1 <= N <= STOM_MAX_POINTS:
+        raise _lib.Rga3Error(f"{name}: {N} points per frame (1..{STOM_MAX_POINTS})")
+    if not 0 <= vip_frame_idx < T:
+        raise _lib.Rga3Error(f"{name}: vip_frame_idx {vip_frame_idx} outside [0, {T})")
+    return T, N
+
+
+def _stom_frames(name, frames, overlay):
+    _need_cuda(frames, overlay)
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3 or frames.shape[0] == 0 or not frames.is_contiguous():
+        raise _lib.Rga3Error(f"{name}: frames are contiguous uint8 [T, H, W, 3], got {frames.dtype} {tuple(frames.shape)}")
+    T, H, W, _ = frames.shape
+    if overlay.dtype != torch.uint8 or tuple(overlay.shape) != (H, W, 4) or not overlay.is_contiguous() or overlay.device != frames.device:
+        raise _lib.Rga3Error(f"{name}: the overlay is contiguous uint8 [{H}, {W}, 4] on {frames.device}, got {overlay.dtype} {tuple(overlay.shape)} on {overlay.device}")
+    return T, H, W
+
+
+def stom_flow(tracks, visibility, vip_frame_idx: int):
+    """tracks f32 [T, N, 2], visibility bool [T, N] -> int32 [T, 4] = {apply, bits of dx, bits of dy, kept points} per frame: rga3.model.STOM.mean_flow against frame
+    ``vip_frame_idx`` (median / MAD filter of the flow magnitudes, fp32 mean of the kept flows), decided and kept on the device.  N <= 16384."""
+    T, N = _stom_points("stom_flow", tracks, visibility, vip_frame_idx)
+    rec = torch.empty((T, 4), dtype=torch.int32, device=tracks.device)
+    _lib.check(_lib.load().rga3_stom_flow(tracks.data_ptr(), visibility.data_ptr(), rec.data_ptr(), T, N, int(vip_frame_idx), _stream()), "stom_flow")
+    return rec
+
+
+def stom_shift_composite(frames, overlay, records, vip_frame_idx: int):
+    """frames uint8 [T, H, W, 3], overlay uint8 [H, W, 4], records of stom_flow -> uint8 [T, H, W, 3]: shift_overlay + composite of rga3.model.STOM per frame (the
+    overlay unshifted on frame ``vip_frame_idx``, frames whose record says skip copied)."""
+    T, H, W = _stom_frames("stom_shift_composite", frames, overlay)
+    _need_cuda(records)
+    if records.dtype != torch.int32 or tuple(records.shape) != (T, 4) or not records.is_contiguous() or records.device != frames.device:
+        raise _lib.Rga3Error(f"stom_shift_composite: records are contiguous int32 [{T}, 4] on {frames.device}, got {records.dtype} {tuple(records.shape)}")
+    if not 0 <= vip_frame_idx < T:
+        raise _lib.Rga3Error(f"stom_shift_composite: vip_frame_idx {vip_frame_idx} outside [0, {T})")
+    out = torch.empty_like(frames)
+    _lib.check(_lib.load().rga3_stom_shift_composite(frames.data_ptr(), overlay.data_ptr(), records.data_ptr(), out.data_ptr(), T, H, W, int(vip_frame_idx), _stream()),
+               "stom_shift_composite")
+    return out
+
+
+def stom_mask_composite(frames, overlay, tracks, visibility, vip_frame_idx: int, spans, ksize: int, half_widths, radius: int):
+    """rga3.model.STOM.warp_point per frame for mask-shaped prompts -> uint8 [T, H, W, 3].  spans = STOM.ellipse_spans(ksize) and half_widths =
+    STOM.circle_half_widths(radius) are host uint8 arrays (they travel as kernel arguments).  The bit-packed masks live in a workspace this module owns per stream."""
+    import numpy as np
+
+    T, H, W = _stom_frames("stom_mask_composite", frames, overlay)
+    Tp, N = _stom_points("stom_mask_composite", tracks, visibility, vip_frame_idx)
+    if Tp != T or tracks.device != frames.device:
+        raise _lib.Rga3Error(f"stom_mask_composite: {Tp} frames of tracks on {tracks.device} for {T} frames on {frames.device}")
+    if not 0 <= ksize <= STOM_MAX_KERNEL:
+        raise _lib.Rga3Error(f"stom_mask_composite: structuring element of {ksize} (0..{STOM_MAX_KERNEL})")
+    spans = np.ascontiguousarray(spans, dtype=np.uint8)
+    half_widths = np.ascontiguousarray(half_widths, dtype=np.uint8)
+    if spans.shape != (max(ksize, 1), 2) or radius < 0 or half_widths.shape != (radius + 1,):
+        raise _lib.Rga3Error(f"stom_mask_composite: spans {spans.shape} / half widths {half_widths.shape} do not fit ksize {ksize} / radius {radius}")
+    L = _lib.load()
+    nws = int(L.rga3_stom_ws_bytes(T, H, W))
+    if nws < 0:
+        raise _lib.Rga3Error("stom_ws_bytes failed: " + _lib.last_error())
+    key = _ws_key(frames.device)
+    ws = _stom_ws.get(key)
+    if ws is None or ws.numel() < nws:
+        ws = _stom_ws[key] = torch.empty(nws, dtype=torch.uint8, device=frames.device)
+    out = torch.empty_like(frames)
+    _lib.check(L.rga3_stom_mask_composite(frames.data_ptr(), overlay.data_ptr(), tracks.data_ptr(), visibility.data_ptr(), out.data_ptr(), ws.data_ptr(), nws, T, H, W, N,
+                                          int(vip_frame_idx), spans.ctypes.data, int(ksize), half_widths.ctypes.data, int(radius), _stream()), "stom_mask_composite")
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ training-step kernels
 def attn_varlen_bwd(q, k, v, o, dout, lse, cu_q, cu_k, max_q: int, max_k: int, scale: float, causal: bool, dq=None, dk=None, dv=None):
     """Gradients of attn_varlen w.r.t. q, k, v (bf16, same [T, H, D] shapes; outputs may be strided views)."""
