@@ -12,9 +12,6 @@
 // Call sites replaced: the autograd of flash_attn_varlen_func / SDPA under train_joint.py:534 (model.backward).
 #include "common.h"
 
-#include <mutex>
-#include <set>
-
 namespace rga3 {
 
 struct AttnBwdArgs {
@@ -469,6 +466,13 @@ __global__ __launch_bounds__(256) void attn_dkv_reduce_kernel(AttnBwdArgs p) {
     *(u32x2*)(p.dv + key * p.dv_st + (long)hk * p.dv_sh + dd) = b;
 }
 
+// One backward launch: gx blocks x gy heads x nseg segments on a 1-D grid (decoded XCD-aware by the kernel from a.gx / a.gy)
+template <auto K>
+static int launch_bwd_grid(AttnBwdArgs& a, int lds, unsigned gx, int gy, int nseg, int nwave, hipStream_t st, const char* name) {
+    a.gx = (int)gx; a.gy = gy;
+    return launch_lds<K>(dim3(gx * (unsigned)gy * (unsigned)nseg), dim3(64 * nwave), lds, st, name, a);
+}
+
 template <int DP>
 static int launch_bwd(const AttnBwdArgs& a0, int nseg, int max_q, int max_k, hipStream_t st) {
     AttnBwdArgs a = a0;
@@ -483,66 +487,24 @@ static int launch_bwd(const AttnBwdArgs& a0, int nseg, int max_q, int max_k, hip
     constexpr int BLOCK_M = NWQ * QT * 16;
     constexpr int LDS_DQ = 2 * BT * (DP * 2 + 32);
     constexpr int LDS_DKV = 2 * BT * (DP * 2 + 32) + 2 * BT * 4;
-    auto prep = [](const void* k, int lds) -> int {   // once per kernel instantiation
-        if (lds <= 48 * 1024) return 0;
-        static std::mutex mu;
-        static std::set<std::pair<const void*, int>> done;   // (kernel, device): the attribute is per device
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-        std::lock_guard<std::mutex> lk(mu);
-        if (done.count({k, dev})) return 0;
-        hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return fail(-(int)e, "attn_bwd: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        done.insert({k, dev});
-        return 0;
-    };
     // (delta = rowsum(dO * O) is computed inside the dQ kernel, which runs first and leaves it in a.delta for the dK / dV kernel)
     const unsigned nqb = (unsigned)cdiv(max_q, BLOCK_M), nkb = (unsigned)cdiv(max_k, 16 * NW);
     const bool pair = a.causal && nqb >= 4 && nkb >= 4;   // balanced causal rows (see the kernels)
-    if (pair) {
-        auto kq = attn_bwd_dq_kernel<DP, QT, NWQ, true>;
-        if (int rc = prep((const void*)kq, LDS_DQ)) return rc;
-        a.gx = (int)((nqb + 1) / 2); a.gy = a.Hq;
-        hipLaunchKernelGGL(kq, dim3((unsigned)a.gx * (unsigned)a.gy * (unsigned)nseg), dim3(64 * NWQ), LDS_DQ, st, a);
-    } else {
-        auto kq = attn_bwd_dq_kernel<DP, QT, NWQ, false>;
-        if (int rc = prep((const void*)kq, LDS_DQ)) return rc;
-        a.gx = (int)nqb; a.gy = a.Hq;
-        hipLaunchKernelGGL(kq, dim3((unsigned)a.gx * (unsigned)a.gy * (unsigned)nseg), dim3(64 * NWQ), LDS_DQ, st, a);
-    }
-    RGA3_CHECK_LAUNCH("attn_bwd_dq_kernel");
-    const unsigned gx = pair ? (nkb + 1) / 2 : nkb;
+    const unsigned gq = pair ? (nqb + 1) / 2 : nqb, gk = pair ? (nkb + 1) / 2 : nkb;
+    if (int rc = pair ? launch_bwd_grid<attn_bwd_dq_kernel<DP, QT, NWQ, true>>(a, LDS_DQ, gq, a.Hq, nseg, NWQ, st, "attn_bwd_dq_kernel")
+                      : launch_bwd_grid<attn_bwd_dq_kernel<DP, QT, NWQ, false>>(a, LDS_DQ, gq, a.Hq, nseg, NWQ, st, "attn_bwd_dq_kernel"))
+        return rc;
     if (a.dkv_ws && a.Hq > a.Hkv) {
-        if (pair) {
-            auto ks_ = attn_bwd_dkv_kernel<DP, NW, true, true>;
-            if (int rc = prep((const void*)ks_, LDS_DKV)) return rc;
-            a.gx = (int)gx; a.gy = a.Hq;
-            hipLaunchKernelGGL(ks_, dim3((unsigned)a.gx * (unsigned)a.gy * (unsigned)nseg), dim3(64 * NW), LDS_DKV, st, a);
-        } else {
-            auto ks_ = attn_bwd_dkv_kernel<DP, NW, true, false>;
-            if (int rc = prep((const void*)ks_, LDS_DKV)) return rc;
-            a.gx = (int)gx; a.gy = a.Hq;
-            hipLaunchKernelGGL(ks_, dim3((unsigned)a.gx * (unsigned)a.gy * (unsigned)nseg), dim3(64 * NW), LDS_DKV, st, a);
-        }
-        RGA3_CHECK_LAUNCH("attn_bwd_dkv_kernel<split>");
+        if (int rc = pair ? launch_bwd_grid<attn_bwd_dkv_kernel<DP, NW, true, true>>(a, LDS_DKV, gk, a.Hq, nseg, NW, st, "attn_bwd_dkv_kernel<split>")
+                          : launch_bwd_grid<attn_bwd_dkv_kernel<DP, NW, true, false>>(a, LDS_DKV, gk, a.Hq, nseg, NW, st, "attn_bwd_dkv_kernel<split>"))
+            return rc;
         const long rows = a.total_k * a.Hkv;
         hipLaunchKernelGGL(attn_dkv_reduce_kernel, dim3((unsigned)cdiv(rows * (a.D / 4), 256)), dim3(256), 0, st, a);
         RGA3_CHECK_LAUNCH("attn_dkv_reduce_kernel");
         return 0;
     }
-    if (pair) {
-        auto kk = attn_bwd_dkv_kernel<DP, NW, false, true>;
-        if (int rc = prep((const void*)kk, LDS_DKV)) return rc;
-        a.gx = (int)gx; a.gy = a.Hkv;
-        hipLaunchKernelGGL(kk, dim3((unsigned)a.gx * (unsigned)a.gy * (unsigned)nseg), dim3(64 * NW), LDS_DKV, st, a);
-    } else {
-        auto kk = attn_bwd_dkv_kernel<DP, NW, false, false>;
-        if (int rc = prep((const void*)kk, LDS_DKV)) return rc;
-        a.gx = (int)gx; a.gy = a.Hkv;
-        hipLaunchKernelGGL(kk, dim3((unsigned)a.gx * (unsigned)a.gy * (unsigned)nseg), dim3(64 * NW), LDS_DKV, st, a);
-    }
-    RGA3_CHECK_LAUNCH("attn_bwd_dkv_kernel");
-    return 0;
+    return pair ? launch_bwd_grid<attn_bwd_dkv_kernel<DP, NW, false, true>>(a, LDS_DKV, gk, a.Hkv, nseg, NW, st, "attn_bwd_dkv_kernel")
+                : launch_bwd_grid<attn_bwd_dkv_kernel<DP, NW, false, false>>(a, LDS_DKV, gk, a.Hkv, nseg, NW, st, "attn_bwd_dkv_kernel");
 }
 
 }  // namespace rga3

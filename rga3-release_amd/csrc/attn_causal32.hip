@@ -447,17 +447,13 @@ __global__ __launch_bounds__(512) void attn_causal32_kernel(AttnArgs p) {
 }
 
 int launch_causal32(const AttnArgs& a, int nseg, int max_q, hipStream_t st) {
-    static LdsGrant lds_grant;
-    if (int rc = grant_dyn_lds((const void*)attn_causal32_kernel, C32_LDS, lds_grant, "attn_causal32")) return rc;
     AttnArgs b = a;
 #ifdef RGA3_AB   // measurement builds only (tools/): ablation mask 1 = no tile DMA in the loop, 2 = no softmax, 4 = no P V, 8 = no K Q^T, 16 = no wait / barrier
     { const char* e = getenv("RGA3_C32_DBG"); b.bk_shift = e ? atoi(e) : 0; }
 #endif
     const unsigned nqb = (unsigned)cdiv(max_q, C32_QB);
     b.gx = (int)((nqb + 1) / 2);
-    hipLaunchKernelGGL(attn_causal32_kernel, dim3((unsigned)b.gx * (unsigned)a.Hq * (unsigned)nseg), dim3(512), C32_LDS, st, b);
-    RGA3_CHECK_LAUNCH("attn_causal32_kernel");
-    return 0;
+    return launch_lds<attn_causal32_kernel>(dim3((unsigned)b.gx * (unsigned)a.Hq * (unsigned)nseg), dim3(512), C32_LDS, st, "attn_causal32_kernel", b);
 }
 
 }  // namespace rga3

@@ -16,7 +16,7 @@
 //  * K/V tiles are register-staged (global_load 16 B -> ds_write_b128) one tile ahead, into rows padded by
 //    32 B so that both the b128 K reads and the transposed V reads are bank-conflict-free.
 #include "attn_args.h"
-#include <type_traits>
+#include "loop_tags.h"
 
 namespace rga3 {
 
@@ -292,8 +292,6 @@ __global__ __launch_bounds__(64 * NWAVE) void attn_fwd_kernel(AttnArgs p) {
         }
     };
 
-    using S0 = std::integral_constant<int, 0>;
-    using S1 = std::integral_constant<int, 1>;
     if (kt_begin < ntiles) load_tile(S0{}, kt_begin);
     if constexpr (RING > 1) { if (kt_begin + 1 < ntiles) load_tile(S1{}, kt_begin + 1); }
     if constexpr (RING > 2) { if (kt_begin + 2 < ntiles) load_tile(std::integral_constant<int, 2>{}, kt_begin + 2); }
@@ -575,26 +573,30 @@ __global__ __launch_bounds__(256) void attn_split_combine_kernel(AttnArgs p) {
     if (p.lse && lane == 0) p.lse[(long)hq * p.total_q + tq] = wsum > 0.f ? (m + log2f(wsum)) * 0.6931471805599453f : -INFINITY;
 }
 
-static bool g_attn_full_tiles = false;  // A/B switch (impl bit 16): keep all DP / 16 output tiles where D <= 80 would need five of six
+// The impl bits of rga3_attn_varlen_fwd, decoded once at the entry point and handed down the dispatch.  All are A/B and parity switches; tests, tools/ and
+// ops.set_causal32 rely on each bit keeping its meaning.
+struct AttnImpl {
+    bool scalar_read;   // 1: the general kernel only, on its scalar-read form (no transposing LDS reads): debug cross-check
+    bool wave4;         // 2: the general kernel only, on 4 waves x QT = 2 where 8 waves would be chosen (benchmark switch)
+    bool no_causal32;   // 4: keep the long causal rows on the general kernel
+    bool win_q16;       // 8: 256-query windows on the 16-rows-per-wave form (two workgroups per window and head)
+    bool full_tiles;    // 16: keep all DP / 16 output tiles where D <= 80 would need five of six
+};
 
 template <int DP, int QT, int NWAVE, bool USE_TR, bool PAIR, int KT = KV_TILE, int DTO = DP / 16>
-static int launch_attn_p(const AttnArgs& a, int nseg, unsigned gx, hipStream_t st) {
+static int launch_attn_p(const AttnArgs& a, const AttnImpl& im, int nseg, unsigned gx, hipStream_t st) {
     if constexpr (DP == 96 && DTO == 6 && !PAIR) {
-        if (a.D <= 80 && !g_attn_full_tiles) return launch_attn_p<DP, QT, NWAVE, USE_TR, PAIR, KT, 5>(a, nseg, gx, st);
+        if (a.D <= 80 && !im.full_tiles) return launch_attn_p<DP, QT, NWAVE, USE_TR, PAIR, KT, 5>(a, im, nseg, gx, st);
     }
     constexpr int LDS = 2 * KT * (DP * 2 + 32);
-    auto kern = attn_fwd_kernel<DP, QT, NWAVE, USE_TR, PAIR, false, false, KT, DTO>;
-    static LdsGrant lds_grant;
-    if (int rc = grant_dyn_lds((const void*)kern, LDS, lds_grant, "attn")) return rc;
     AttnArgs b = a;
     b.gx = (int)gx;
-    hipLaunchKernelGGL(kern, dim3(gx * (unsigned)a.Hq * (unsigned)nseg), dim3(64 * NWAVE), LDS, st, b);
-    RGA3_CHECK_LAUNCH("attn_fwd_kernel");
-    return 0;
+    return launch_lds<attn_fwd_kernel<DP, QT, NWAVE, USE_TR, PAIR, false, false, KT, DTO>>(dim3(gx * (unsigned)a.Hq * (unsigned)nseg), dim3(64 * NWAVE), LDS, st,
+                                                                                          "attn_fwd_kernel", b);
 }
 
 template <int DP, int QT, int NWAVE, bool USE_TR>
-static int launch_attn(const AttnArgs& a, int nseg, int max_q, hipStream_t st) {
+static int launch_attn(const AttnArgs& a, const AttnImpl& im, int nseg, int max_q, hipStream_t st) {
     constexpr int BLOCK_M = NWAVE * QT * 16;
     const unsigned nqb = (unsigned)cdiv(max_q, BLOCK_M);
     // the paired-q-block form only for the long causal rows of the decoder (D = 64 / 128, 8 waves): elsewhere it would only
@@ -603,89 +605,92 @@ static int launch_attn(const AttnArgs& a, int nseg, int max_q, hipStream_t st) {
         if (a.causal && nqb >= 4) {
             // the decoder's causal rows walk 128-key tiles: half the barriers, softmax rescales and tile bookkeeping per key (same 205 VGPRs: one register slot
             // of four loads instead of three of two) -- 66.3 -> 61.5 us at S = 2112, 219.5 -> 203.6 us at S = 4160 on one box
-            if constexpr (DP == 128 && QT == 1) return launch_attn_p<DP, QT, NWAVE, USE_TR, true, 128>(a, nseg, (nqb + 1) / 2, st);
-            else return launch_attn_p<DP, QT, NWAVE, USE_TR, true>(a, nseg, (nqb + 1) / 2, st);
+            if constexpr (DP == 128 && QT == 1) return launch_attn_p<DP, QT, NWAVE, USE_TR, true, 128>(a, im, nseg, (nqb + 1) / 2, st);
+            else return launch_attn_p<DP, QT, NWAVE, USE_TR, true>(a, im, nseg, (nqb + 1) / 2, st);
         }
     }
     if (a.nsplit > 1) {
         constexpr int LDS = 2 * KV_TILE * (DP * 2 + 32);
-        auto kern = attn_fwd_kernel<DP, QT, NWAVE, USE_TR, false, true>;
-        static LdsGrant lds_grant;
-        if (int rc = grant_dyn_lds((const void*)kern, LDS, lds_grant, "attn")) return rc;
         AttnArgs b = a;
         b.gx = (int)(nqb * (unsigned)a.nsplit);
-        hipLaunchKernelGGL(kern, dim3(nqb * (unsigned)a.nsplit * (unsigned)a.Hq * (unsigned)nseg), dim3(64 * NWAVE), LDS, st, b);
-        RGA3_CHECK_LAUNCH("attn_fwd_kernel<split>");
+        if (int rc = launch_lds<attn_fwd_kernel<DP, QT, NWAVE, USE_TR, false, true>>(dim3(nqb * (unsigned)a.nsplit * (unsigned)a.Hq * (unsigned)nseg), dim3(64 * NWAVE),
+                                                                                   LDS, st, "attn_fwd_kernel<split>", b))
+            return rc;
         hipLaunchKernelGGL(attn_split_combine_kernel, dim3((unsigned)cdiv(a.total_q * a.Hq, 4)), dim3(256), 0, st, a);
         RGA3_CHECK_LAUNCH("attn_split_combine_kernel");
         return 0;
     }
     // 128-key tiles also for the non-paired long rows at D = 128 (3 280 -> 3 159 us at B16 H64 L2048); at D = 64 they lose (1 633 -> 2 000 us: the 8 loads of a
     // tile leave one register slot instead of three)
-    if constexpr (DP == 128 && QT == 1 && NWAVE == 8) return launch_attn_p<DP, QT, NWAVE, USE_TR, false, 128>(a, nseg, nqb, st);
-    else return launch_attn_p<DP, QT, NWAVE, USE_TR, false>(a, nseg, nqb, st);
+    if constexpr (DP == 128 && QT == 1 && NWAVE == 8) return launch_attn_p<DP, QT, NWAVE, USE_TR, false, 128>(a, im, nseg, nqb, st);
+    else return launch_attn_p<DP, QT, NWAVE, USE_TR, false>(a, im, nseg, nqb, st);
 }
 
 // RoPE-while-loading variant: windows of <= 64 queries (one query block of 4 waves x 16 rows per segment and head)
 template <int DP>
 static int launch_rope_win(const AttnArgs& a, int nseg, hipStream_t st) {
     constexpr int LDS = 2 * KV_TILE * (DP * 2 + 32);
-    auto kern = attn_fwd_kernel<DP, 1, 4, true, false, false, true>;
-    static LdsGrant lds_grant;
-    if (int rc = grant_dyn_lds((const void*)kern, LDS, lds_grant, "attn")) return rc;
     AttnArgs b = a;
     b.gx = 1;
-    hipLaunchKernelGGL(kern, dim3((unsigned)a.Hq * (unsigned)nseg), dim3(256), LDS, st, b);
-    RGA3_CHECK_LAUNCH("attn_fwd_kernel<rope>");
-    return 0;
+    return launch_lds<attn_fwd_kernel<DP, 1, 4, true, false, false, true>>(dim3((unsigned)a.Hq * (unsigned)nseg), dim3(256), LDS, st, "attn_fwd_kernel<rope>", b);
 }
 
 template <int DP, int NW, int QT, bool ROPE = false, int DTO = DP / 16>
 static int launch_win(const AttnArgs& a, int nseg, int max_q, int max_k, hipStream_t st) {
     const int chr = (((a.D * 2 + 15) >> 4) | 1);
     const int nrows = (max_k + 63) & ~63;
-    const int lds = 2 * nrows * chr * 16 + 256;
-    auto kern = attn_win_kernel<DP, NW, QT, ROPE, DTO>;
-    static LdsGrant lds_grant;   // per device, grows monotonically; a racing second setter only repeats the call
-    if (int rc = grant_dyn_lds((const void*)kern, lds, lds_grant, "attn")) return rc;
+    const int lds = 2 * nrows * chr * 16 + 256;   // grows with max_k: launch_lds re-grants when a later call needs more
     AttnArgs b = a;
     b.gx = (int)cdiv(max_q, 16 * QT * NW);
-    hipLaunchKernelGGL(kern, dim3((unsigned)b.gx * (unsigned)a.Hq * (unsigned)nseg), dim3(64 * NW), lds, st, b);
-    RGA3_CHECK_LAUNCH("attn_win_kernel");
-    return 0;
+    return launch_lds<attn_win_kernel<DP, NW, QT, ROPE, DTO>>(dim3((unsigned)b.gx * (unsigned)a.Hq * (unsigned)nseg), dim3(64 * NW), lds, st, "attn_win_kernel", b);
 }
 
-static int g_attn_variant = 0;  // 0: auto, 1: force 4 waves x QT=2, 2: force 8 waves x QT=1 (benchmark switch, read-only after init)
-
 template <int DP, bool USE_TR>
-static int launch_dp(const AttnArgs& a, int nseg, int max_q, hipStream_t st) {
+static int launch_dp(const AttnArgs& a, const AttnImpl& im, int nseg, int max_q, hipStream_t st) {
     if constexpr (DP == 128 || DP == 64) {
         // long sequences: 8 waves x 16 query rows keeps the register footprint near 110 VGPRs (4 waves/SIMD) instead of
         // one 300-register wave per SIMD
         // (measured, round 2: 64-row paired query blocks on 4 waves -- twice the workgroups, two per CU at S = 2112 -- are slower: 73.8 vs 65.9 us)
-        if (max_q > 64 && g_attn_variant != 1) return launch_attn<DP, 1, 8, USE_TR>(a, nseg, max_q, st);
+        if (max_q > 64 && !im.wave4) return launch_attn<DP, 1, 8, USE_TR>(a, im, nseg, max_q, st);
     }
     if constexpr (DP == 96) {
         // (8 waves x 16 rows for the 4096-token global blocks: 1 428 vs 1 150 us -- the 32-row waves halve the K / V fragment reads per query row)
         // a whole 256-token window (Hiera stage 3) per workgroup: K / V staged once instead of once per 128-row half
-        if (!a.causal && max_q >= 256 && max_q % 256 == 0 && g_attn_variant != 1) return launch_attn<DP, 2, 8, USE_TR>(a, nseg, max_q, st);
+        if (!a.causal && max_q >= 256 && max_q % 256 == 0 && !im.wave4) return launch_attn<DP, 2, 8, USE_TR>(a, im, nseg, max_q, st);
     }
     if constexpr (DP >= 256) {
-        return launch_attn<DP, 1, 4, USE_TR>(a, nseg, max_q, st);
+        return launch_attn<DP, 1, 4, USE_TR>(a, im, nseg, max_q, st);
     } else {
-        if (max_q <= 64) return launch_attn<DP, 1, 4, USE_TR>(a, nseg, max_q, st);
-        return launch_attn<DP, 2, 4, USE_TR>(a, nseg, max_q, st);
+        if (max_q <= 64) return launch_attn<DP, 1, 4, USE_TR>(a, im, nseg, max_q, st);
+        return launch_attn<DP, 2, 4, USE_TR>(a, im, nseg, max_q, st);
     }
 }
 
 template <bool USE_TR>
-static int launch_any(const AttnArgs& a, int nseg, int max_q, hipStream_t st) {
+static int launch_any(const AttnArgs& a, const AttnImpl& im, int nseg, int max_q, hipStream_t st) {
     const int D = a.D;
-    if (D <= 32) return launch_dp<32, USE_TR>(a, nseg, max_q, st);
-    if (D <= 64) return launch_dp<64, USE_TR>(a, nseg, max_q, st);
-    if (D <= 96) return launch_dp<96, USE_TR>(a, nseg, max_q, st);
-    if (D <= 128) return launch_dp<128, USE_TR>(a, nseg, max_q, st);
-    return launch_dp<256, USE_TR>(a, nseg, max_q, st);
+    if (D <= 32) return launch_dp<32, USE_TR>(a, im, nseg, max_q, st);
+    if (D <= 64) return launch_dp<64, USE_TR>(a, im, nseg, max_q, st);
+    if (D <= 96) return launch_dp<96, USE_TR>(a, im, nseg, max_q, st);
+    if (D <= 128) return launch_dp<128, USE_TR>(a, im, nseg, max_q, st);
+    return launch_dp<256, USE_TR>(a, im, nseg, max_q, st);
+}
+
+// The arguments both forward entry points share; no rope tables, no block-diagonal packing, no key split until the caller sets them.
+static AttnArgs attn_args(const void* q, const void* k, const void* v, void* o, float* lse, const int32_t* cu_q, const int32_t* cu_k, int64_t total_q, int Hq, int Hkv,
+                          int D, int64_t q_st, int64_t q_sh, int64_t k_st, int64_t k_sh, int64_t v_st, int64_t v_sh, int64_t o_st, int64_t o_sh, float scale, int causal) {
+    AttnArgs a;
+    a.q = (const unsigned short*)q; a.k = (const unsigned short*)k; a.v = (const unsigned short*)v;
+    a.o = (unsigned short*)o; a.lse = lse; a.cu_q = cu_q; a.cu_k = cu_k;
+    a.q_st = q_st; a.q_sh = q_sh; a.k_st = k_st; a.k_sh = k_sh; a.v_st = v_st; a.v_sh = v_sh; a.o_st = o_st; a.o_sh = o_sh;
+    a.Hq = Hq; a.Hkv = Hkv; a.D = D;
+    a.total_q = total_q;
+    a.scale_log2 = scale * 1.4426950408889634f;
+    a.causal = causal;
+    a.rope_cos = a.rope_sin = a.rope_kcos = a.rope_ksin = nullptr;
+    a.bq_shift = a.bk_shift = -1;
+    a.split_o = nullptr; a.split_lse = nullptr; a.nsplit = 1; a.gx = 1;
+    return a;
 }
 
 }  // namespace rga3
@@ -709,27 +714,14 @@ extern "C" int rga3_attn_varlen_fwd(const void* q, const void* k, const void* v,
     RGA3_CHECK_ARG(nseg <= 65535 && Hq <= 65535, "attn: grid dims too large");
     RGA3_CHECK_ARG(k_st < (1 << 24) && v_st < (1 << 24), "attn: k/v row stride too large for 32-bit tile offsets");
     RGA3_CHECK_ARG(impl >= 0 && impl <= 31, "attn: impl %d", impl);
-    g_attn_full_tiles = (impl & 16) != 0;
-    const bool win_q16 = (impl & 8) != 0;       // A/B switch: 256-query windows on the 16-rows-per-wave form (two workgroups per window and head)
-    g_attn_variant = (impl & 2) ? 1 : 0;
-    const bool no_causal32 = (impl & 4) != 0;   // A/B and parity switch: keep the long causal rows on the general kernel
-    impl &= 1;
-    AttnArgs a;
-    a.q = (const unsigned short*)q; a.k = (const unsigned short*)k; a.v = (const unsigned short*)v;
-    a.o = (unsigned short*)o; a.lse = lse; a.cu_q = cu_q; a.cu_k = cu_k;
-    a.q_st = q_st; a.q_sh = q_sh; a.k_st = k_st; a.k_sh = k_sh; a.v_st = v_st; a.v_sh = v_sh; a.o_st = o_st; a.o_sh = o_sh;
-    a.Hq = Hq; a.Hkv = Hkv; a.D = D;
-    a.total_q = total_q;
-    a.scale_log2 = scale * 1.4426950408889634f;
-    a.causal = causal;
-    a.rope_cos = a.rope_sin = a.rope_kcos = a.rope_ksin = nullptr;
-    // split the key range when the grid would leave most CUs idle: <= 8 slices, >= 8 key tiles each, workspace permitting
+    const AttnImpl im = {(impl & 1) != 0, (impl & 2) != 0, (impl & 4) != 0, (impl & 8) != 0, (impl & 16) != 0};
+    const bool special = !im.scalar_read && !im.wave4;   // the kernels beside the general one are open to this call
+    AttnArgs a = attn_args(q, k, v, o, lse, cu_q, cu_k, total_q, Hq, Hkv, D, q_st, q_sh, k_st, k_sh, v_st, v_sh, o_st, o_sh, scale, causal);
     RGA3_CHECK_ARG((block_q == 0) == (block_k == 0) && block_q >= 0 && (block_q & (block_q - 1)) == 0 && (block_k & (block_k - 1)) == 0,
                    "attn: block_q / block_k must both be 0 or powers of two (got %d, %d)", block_q, block_k);
     RGA3_CHECK_ARG(block_q == 0 || !causal, "attn: block-diagonal packing is for non-causal windows");
-    a.bq_shift = a.bk_shift = -1;
     if (block_q > 0) { a.bq_shift = __builtin_ctz((unsigned)block_q); a.bk_shift = __builtin_ctz((unsigned)block_k); }
-    a.split_o = nullptr; a.split_lse = nullptr; a.nsplit = 1; a.gx = 1;
+    // split the key range when the grid would leave most CUs idle: <= 8 slices, >= 8 key tiles each, workspace permitting
     if (split_ws && !causal && block_q == 0 && D % 4 == 0 && max_k >= 1024) {
         const long wgs = (long)cdiv(max_q, 64) * Hq * nseg;
         int ns = (int)(256 / (wgs > 0 ? wgs : 1));
@@ -746,9 +738,9 @@ extern "C" int rga3_attn_varlen_fwd(const void* q, const void* k, const void* v,
     // long causal rows at D = 128 (the decoder's prefill / training rows): 32-row waves balanced over the key range (attn_causal32.hip)
     // (its output rows leave by 16-byte stores: an 8-byte-aligned `o` view, legal for the general kernel, stays there)
     const bool o16 = (((uintptr_t)o) & 15) == 0 && o_st % 8 == 0 && o_sh % 8 == 0;
-    if (impl == 0 && g_attn_variant == 0 && !no_causal32 && o16 && causal && D == 128 && max_q >= 256 && block_q == 0) return launch_causal32(a, nseg, max_q, st);
+    if (special && !im.no_causal32 && o16 && causal && D == 128 && max_q >= 256 && block_q == 0) return launch_causal32(a, nseg, max_q, st);
     // whole-segment-in-LDS window kernel: non-causal, key range known and <= 256, D <= 96, 16-byte rows (impl bit 1 keeps the pipelined kernel: A/B)
-    if (impl == 0 && g_attn_variant == 0 && !causal && a.nsplit == 1 && max_k > 0 && max_k <= 256 && D <= 96 && D % 8 == 0 &&
+    if (special && !causal && a.nsplit == 1 && max_k > 0 && max_k <= 256 && D <= 96 && D % 8 == 0 &&
         (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) == 0 && q_st % 8 == 0 && q_sh % 8 == 0 && k_st % 8 == 0 && k_sh % 8 == 0 && v_st % 8 == 0 && v_sh % 8 == 0) {
         // (4 waves x 32 rows per 256-token window -- half the fragment reads per row, one wave fewer per SIMD -- measured slower: 129 vs 112 us)
         // (64 < D <= 80 -- Hiera's 72, the ViT's 80 -- spans 5 of the 6 sixteen-column output tiles of DP = 96: a sixth of the P V work and of the V fragment reads)
@@ -759,11 +751,11 @@ extern "C" int rga3_attn_varlen_fwd(const void* q, const void* k, const void* v,
         // one workgroup per CU walking (window, head) items with the next item's K | V images arriving by LDS-DMA into a second LDS buffer while this one is
         // multiplied, all loads and the counted wait in one inline-asm statement -- was built, bit-checked and measured at 122 us: with one workgroup per CU an
         // item's 72 KiB take ~13 us to arrive, two independent workgroups per CU keep twice the bytes in flight; profiles/r06_hiera_attn_probe.log)
-        if (D > 64 && max_q > 128 && !win_q16) return (D <= 80) ? launch_win<96, 8, 2, false, 5>(a, nseg, max_q, max_k, st) : launch_win<96, 8, 2>(a, nseg, max_q, max_k, st);
+        if (D > 64 && max_q > 128 && !im.win_q16) return (D <= 80) ? launch_win<96, 8, 2, false, 5>(a, nseg, max_q, max_k, st) : launch_win<96, 8, 2>(a, nseg, max_q, max_k, st);
         return (D <= 64) ? launch_win<64, 8, 1>(a, nseg, max_q, max_k, st) : (D <= 80) ? launch_win<96, 8, 1, false, 5>(a, nseg, max_q, max_k, st) : launch_win<96, 8, 1>(a, nseg, max_q, max_k, st);
     }
-    if (impl == 0) return launch_any<true>(a, nseg, max_q, st);
-    return launch_any<false>(a, nseg, max_q, st);
+    if (!im.scalar_read) return launch_any<true>(a, im, nseg, max_q, st);
+    return launch_any<false>(a, im, nseg, max_q, st);
 }
 
 extern "C" int rga3_attn_varlen_fwd_rope(const void* q, const void* k, const void* v, void* o, float* lse, const int32_t* cu_q, const int32_t* cu_k, int nseg,
@@ -782,16 +774,8 @@ extern "C" int rga3_attn_varlen_fwd_rope(const void* q, const void* k, const voi
                        (((uintptr_t)o) & 7) == 0, "attn_varlen_fwd_rope: pointer alignment");
     RGA3_CHECK_ARG(k_st < (1 << 24) && v_st < (1 << 24), "attn_varlen_fwd_rope: k/v row stride too large");
     RGA3_CHECK_ARG(!c32 || ((((uintptr_t)o) & 15) == 0 && o_st % 8 == 0 && o_sh % 8 == 0), "attn_varlen_fwd_rope: the causal D = 128 rows write 16-byte pieces: o must be 16-byte aligned, strides multiples of 8");
-    AttnArgs a;
-    a.q = (const unsigned short*)q; a.k = (const unsigned short*)k; a.v = (const unsigned short*)v;
-    a.o = (unsigned short*)o; a.lse = lse; a.cu_q = cu_q; a.cu_k = cu_k;
-    a.q_st = q_st; a.q_sh = q_sh; a.k_st = k_st; a.k_sh = k_sh; a.v_st = v_st; a.v_sh = v_sh; a.o_st = o_st; a.o_sh = o_sh;
-    a.Hq = Hq; a.Hkv = Hkv; a.D = D; a.total_q = total_q;
-    a.scale_log2 = scale * 1.4426950408889634f;
-    a.causal = causal;
+    AttnArgs a = attn_args(q, k, v, o, lse, cu_q, cu_k, total_q, Hq, Hkv, D, q_st, q_sh, k_st, k_sh, v_st, v_sh, o_st, o_sh, scale, causal);
     a.rope_cos = cos_q; a.rope_sin = sin_q; a.rope_kcos = cos_k; a.rope_ksin = sin_k;
-    a.bq_shift = a.bk_shift = -1;
-    a.split_o = nullptr; a.split_lse = nullptr; a.nsplit = 1; a.gx = 1;
     hipStream_t st = (hipStream_t)stream;
     if (c32) return launch_causal32(a, nseg, max_q, st);
 #ifdef RGA3_AB   // measurement builds only (tools/): the product library has one behaviour

@@ -13,7 +13,8 @@ namespace rga3 {
     } while (0)
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a PER-DEVICE attribute of a kernel: a process that launches on a second GPU must set it there too
-// (ADVICE r3).  One LdsGrant per kernel instantiation (a function-local static at the launch site) remembers the bytes granted on each device.
+// (ADVICE r3).  One LdsGrant per kernel instantiation (the function-local static of launch_lds) remembers the bytes granted on each device; it grows
+// monotonically, and a racing second setter only repeats the call.
 struct LdsGrant { int bytes[16] = {0}; };
 inline int grant_dyn_lds(const void* kern, int bytes, LdsGrant& g, const char* name) {
     if (bytes <= 48 * 1024) return 0;
@@ -24,6 +25,17 @@ inline int grant_dyn_lds(const void* kern, int bytes, LdsGrant& g, const char* n
     hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     if (e != hipSuccess) return fail(-(int)e, "%s: hipFuncSetAttribute(%d B dynamic LDS): %s", name, bytes, hipGetErrorString(e));
     if (tracked) g.bytes[dev] = bytes;
+    return 0;
+}
+
+// Every launch with dynamic LDS goes through here: grant `lds` bytes to kernel K on this device if it has less, launch, check.  `lds` is the byte count of
+// THIS launch (a kernel sized at run time passes its actual need every time).
+template <auto K, class... A>
+int launch_lds(dim3 grid, dim3 block, int lds, hipStream_t st, const char* name, const A&... args) {
+    static LdsGrant grant;
+    if (int rc = grant_dyn_lds((const void*)K, lds, grant, name)) return rc;
+    hipLaunchKernelGGL(K, grid, block, lds, st, args...);
+    RGA3_CHECK_LAUNCH(name);
     return 0;
 }
 
@@ -51,6 +63,22 @@ __device__ __forceinline__ unsigned int pack_bf2(float lo, float hi) {
     v[1] = (__bf16)hi;
     return __builtin_bit_cast(unsigned int, v);
 }
+// eight packed bf16 (one 16-byte load) <-> eight floats
+__device__ __forceinline__ void unpack8(const u32x4& v, float* f) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        f[2 * i] = __uint_as_float(v[i] << 16);
+        f[2 * i + 1] = __uint_as_float(v[i] & 0xffff0000u);
+    }
+}
+__device__ __forceinline__ u32x4 pack8(const float* f) {
+    u32x4 v;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) v[i] = pack_bf2(f[2 * i], f[2 * i + 1]);
+    return v;
+}
+// the value a bf16 store and reload would give back
+__device__ __forceinline__ float bf16_round(float v) { return bf2f(f2bf(v)); }
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -68,7 +96,7 @@ __device__ __forceinline__ float wave_max(float v) {
 __device__ __forceinline__ float swiglu_fwd_elem(float g, float u) {
 #pragma clang fp contract(off)
     const float silu = g / (1.f + __expf(-g));
-    return __uint_as_float(((unsigned)f2bf(silu)) << 16) * u;
+    return bf16_round(silu) * u;
 }
 __device__ __forceinline__ void swiglu_bwd_elem(float g, float u, float d, float& dg, float& du) {
 #pragma clang fp contract(off)
@@ -79,6 +107,17 @@ __device__ __forceinline__ void swiglu_bwd_elem(float g, float u, float d, float
 }
 
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// 1-D grid for a grid-stride kernel over `total` items: one block per `per_block` items, at least one, at most `cap` (32 blocks on each of 256 CUs)
+static inline unsigned grid1d(long total, int per_block = 256, long cap = 256L * 32) {
+    long b = cdiv(total, per_block);
+    if (b < 1) b = 1;
+    return (unsigned)(b > cap ? cap : b);
+}
+
+// bf16 storage as the entry points cast their void* arguments
+typedef const unsigned short* cus;
+typedef unsigned short* us;
 
 // number of XCDs on MI355X (MI355X_MICROARCH.md chip table); used only for speed (L2 affinity), never correctness
 constexpr int kNumXCD = 8;

@@ -5,20 +5,6 @@
 
 namespace rga3 {
 
-__device__ __forceinline__ void u8_(const u32x4& v, float* f) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        f[2 * i] = __uint_as_float(v[i] << 16);
-        f[2 * i + 1] = __uint_as_float(v[i] & 0xffff0000u);
-    }
-}
-__device__ __forceinline__ u32x4 p8_(const float* f) {
-    u32x4 v;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = pack_bf2(f[2 * i], f[2 * i + 1]);
-    return v;
-}
-
 // y = (x - mean) * r * w + b.  dx = r * (g - mean(g) - xhat * mean(g * xhat)), g = dy * w;  dw += dy * xhat, db += dy.
 // One wave per row (dim <= 512*MAXC/8...), a workgroup walks ROWS_PER_WG rows and reduces dw/db in registers -> LDS -> atomics.
 template <int MAXC>
@@ -43,7 +29,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const unsigned short
                 xb[i] = *(const u32x4*)(x + row * dim + ch * 8);
                 db_[i] = *(const u32x4*)(dy + row * dim + ch * 8);
                 float f[8];
-                u8_(xb[i], f);
+                unpack8(xb[i], f);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) s1 += f[e];
             }
@@ -55,7 +41,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const unsigned short
             const int ch = lane + i * 64;
             if (ch < nch) {
                 float f[8];
-                u8_(xb[i], f);
+                unpack8(xb[i], f);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) { float d = f[e] - mean; s2 += d * d; }
             }
@@ -67,9 +53,9 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const unsigned short
             const int ch = lane + i * 64;
             if (ch < nch) {
                 float fx[8], fd[8], fw[8];
-                u8_(xb[i], fx);
-                u8_(db_[i], fd);
-                u8_(*(const u32x4*)(w + ch * 8), fw);
+                unpack8(xb[i], fx);
+                unpack8(db_[i], fd);
+                unpack8(*(const u32x4*)(w + ch * 8), fw);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     const float xh = (fx[e] - mean) * r;
@@ -88,15 +74,15 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const unsigned short
             const int ch = lane + i * 64;
             if (ch < nch) {
                 float fx[8], fd[8], fw[8], o[8];
-                u8_(xb[i], fx);
-                u8_(db_[i], fd);
-                u8_(*(const u32x4*)(w + ch * 8), fw);
+                unpack8(xb[i], fx);
+                unpack8(db_[i], fd);
+                unpack8(*(const u32x4*)(w + ch * 8), fw);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     const float xh = (fx[e] - mean) * r;
                     o[e] = r * (fd[e] * fw[e] - sg - xh * sgx);
                 }
-                *(u32x4*)(dx + row * dim + ch * 8) = p8_(o);
+                *(u32x4*)(dx + row * dim + ch * 8) = pack8(o);
             }
         }
     }
@@ -130,7 +116,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_rows_kernel(const unsigned 
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int ch = lane % G, sub = lane / G;
     float fw[8], aw[8], ab[8];
-    u8_(*(const u32x4*)(w + ch * 8), fw);
+    unpack8(*(const u32x4*)(w + ch * 8), fw);
 #pragma unroll
     for (int e = 0; e < 8; ++e) { aw[e] = 0.f; ab[e] = 0.f; }
     for (long base = ((long)blockIdx.x * 4 + wv) * RPW; base < rows; base += (long)gridDim.x * 4 * RPW) {
@@ -142,8 +128,8 @@ __global__ __launch_bounds__(256) void layernorm_bwd_rows_kernel(const unsigned 
             vx = *(const u32x4*)(x + row * DIM + ch * 8);
             vd = *(const u32x4*)(dy + row * DIM + ch * 8);
         }
-        u8_(vx, fx);
-        u8_(vd, fd);
+        unpack8(vx, fx);
+        unpack8(vd, fd);
         float s1 = 0.f;
 #pragma unroll
         for (int e = 0; e < 8; ++e) s1 += fx[e];
@@ -173,7 +159,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_rows_kernel(const unsigned 
             float o8[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) o8[e] = r * (fd[e] * fw[e] - sg - xh[e] * sgx);
-            *(u32x4*)(dx + row * DIM + ch * 8) = p8_(o8);
+            *(u32x4*)(dx + row * DIM + ch * 8) = pack8(o8);
         }
     }
     if (part) {
@@ -220,14 +206,14 @@ __global__ __launch_bounds__(256) void colsum_partials_kernel(const unsigned sho
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 float f[8];
-                u8_(v[j], f);
+                unpack8(v[j], f);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) acc[e] += f[e];
             }
         }
         for (; r < r1; r += RS) {
             float f[8];
-            u8_(*(const u32x4*)(px + r * ld), f);
+            unpack8(*(const u32x4*)(px + r * ld), f);
 #pragma unroll
             for (int e = 0; e < 8; ++e) acc[e] += f[e];
         }
@@ -376,10 +362,10 @@ __global__ __launch_bounds__(256) void mask_product_kernel(const unsigned short*
     const int ch = threadIdx.x % CH, sub = threadIdx.x / CH;
     float hy[NM][8];
 #pragma unroll
-    for (int m = 0; m < NM; ++m) u8_(*(const u32x4*)(hyper + (b * NM + m) * C + ch * 8), hy[m]);
+    for (int m = 0; m < NM; ++m) unpack8(*(const u32x4*)(hyper + (b * NM + m) * C + ch * 8), hy[m]);
     for (long p = (long)blockIdx.x * PPB + sub; p < P; p += (long)gridDim.x * PPB) {
         float f[8], acc[NM];
-        u8_(*(const u32x4*)(up + (b * P + p) * C + ch * 8), f);
+        unpack8(*(const u32x4*)(up + (b * P + p) * C + ch * 8), f);
 #pragma unroll
         for (int m = 0; m < NM; ++m) {
             float a = 0.f;
@@ -410,7 +396,7 @@ __global__ __launch_bounds__(256) void mask_product_bwd_kernel(const float* __re
     float hy[NM][8], dh[NM][8];
 #pragma unroll
     for (int m = 0; m < NM; ++m) {
-        u8_(*(const u32x4*)(hyper + (b * NM + m) * C + ch * 8), hy[m]);
+        unpack8(*(const u32x4*)(hyper + (b * NM + m) * C + ch * 8), hy[m]);
 #pragma unroll
         for (int e = 0; e < 8; ++e) dh[m][e] = 0.f;
     }
@@ -419,7 +405,7 @@ __global__ __launch_bounds__(256) void mask_product_bwd_kernel(const float* __re
 #pragma unroll
         for (int m = 0; m < NM; ++m) g[m] = dmasks[(b * NM + m) * P + p];
         const long off = (b * P + p) * C + ch * 8;
-        u8_(*(const u32x4*)(up + off), f);
+        unpack8(*(const u32x4*)(up + off), f);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             float a = 0.f;
@@ -430,7 +416,7 @@ __global__ __launch_bounds__(256) void mask_product_bwd_kernel(const float* __re
             }
             o[e] = a;
         }
-        *(u32x4*)(dup + off) = p8_(o);
+        *(u32x4*)(dup + off) = pack8(o);
     }
     // fold the pixel groups of the wave (lanes with equal ch), then the four waves
 #pragma unroll
@@ -491,17 +477,9 @@ __global__ __launch_bounds__(256) void bce_dice_grad_kernel(const float* __restr
     }
 }
 
-static inline unsigned gd(long total, long cap = 256L * 32) {
-    long b = cdiv(total, 256);
-    if (b < 1) b = 1;
-    return (unsigned)(b > cap ? cap : b);
-}
-
 }  // namespace rga3
 
 using namespace rga3;
-typedef const unsigned short* cus;
-typedef unsigned short* us;
 
 static int ln_bwd_groups(int64_t dim) {
     return (dim == 16 || dim == 32 || dim == 64 || dim == 128 || dim == 256 || dim == 512) ? (int)(dim / 8) : 0;
@@ -610,14 +588,14 @@ extern "C" int rga3_colsum(const void* x, float* out, int64_t rows, int64_t cols
 
 extern "C" int rga3_act(const void* a, const void* dy, void* out, int64_t n, int kind, void* stream) {
     RGA3_CHECK_ARG(a && out && n > 0 && kind >= 0 && kind <= 2 && (kind == 0 || dy), "act: bad args");
-    hipLaunchKernelGGL(act_kernel, dim3(gd(n)), dim3(256), 0, (hipStream_t)stream, (cus)a, (cus)dy, (us)out, (long)n, kind);
+    hipLaunchKernelGGL(act_kernel, dim3(grid1d(n)), dim3(256), 0, (hipStream_t)stream, (cus)a, (cus)dy, (us)out, (long)n, kind);
     RGA3_CHECK_LAUNCH("act");
     return 0;
 }
 
 extern "C" int rga3_bilinear_bwd(const float* dout, float* din, const int32_t* plane_idx, int64_t N, int Hi, int Wi, int Ho, int Wo, void* stream) {
     RGA3_CHECK_ARG(dout && din && N > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0, "bilinear_bwd: bad args");
-    hipLaunchKernelGGL(bilinear_bwd_gather_kernel, dim3(gd(N * (long)Hi * Wi)), dim3(256), 0, (hipStream_t)stream, dout, din, plane_idx, (long)N, Hi, Wi, Ho, Wo);
+    hipLaunchKernelGGL(bilinear_bwd_gather_kernel, dim3(grid1d(N * (long)Hi * Wi)), dim3(256), 0, (hipStream_t)stream, dout, din, plane_idx, (long)N, Hi, Wi, Ho, Wo);
     RGA3_CHECK_LAUNCH("bilinear_bwd");
     return 0;
 }
@@ -666,7 +644,7 @@ extern "C" int rga3_mask_product_bwd(const float* dmasks, const void* hyper, con
 
 extern "C" int rga3_pixel_shuffle2x_bwd(const void* dout, void* dg, int64_t F, int H, int W, int Co, void* stream) {
     RGA3_CHECK_ARG(dout && dg && F > 0 && Co % 8 == 0, "pixel_shuffle2x_bwd: bad args");
-    hipLaunchKernelGGL(pixel_shuffle_bwd_kernel, dim3(gd(F * 4L * H * W * (Co / 8))), dim3(256), 0, (hipStream_t)stream, (cus)dout, (us)dg, (long)F, H, W, Co);
+    hipLaunchKernelGGL(pixel_shuffle_bwd_kernel, dim3(grid1d(F * 4L * H * W * (Co / 8))), dim3(256), 0, (hipStream_t)stream, (cus)dout, (us)dg, (long)F, H, W, Co);
     RGA3_CHECK_LAUNCH("pixel_shuffle2x_bwd");
     return 0;
 }
@@ -674,7 +652,7 @@ extern "C" int rga3_pixel_shuffle2x_bwd(const void* dout, void* dg, int64_t F, i
 extern "C" int rga3_bce_dice_grad(const float* logits, const float* targets, const float* sums4, float* dlogits, int64_t n_masks, int64_t hw,
                                   float coef_bce, float coef_dice, void* stream) {
     RGA3_CHECK_ARG(logits && targets && sums4 && dlogits && n_masks > 0 && hw > 0, "bce_dice_grad: bad args");
-    hipLaunchKernelGGL(bce_dice_grad_kernel, dim3(gd(n_masks * hw)), dim3(256), 0, (hipStream_t)stream, logits, targets, sums4, dlogits, (long)n_masks,
+    hipLaunchKernelGGL(bce_dice_grad_kernel, dim3(grid1d(n_masks * hw)), dim3(256), 0, (hipStream_t)stream, logits, targets, sums4, dlogits, (long)n_masks,
                        (long)hw, coef_bce, coef_dice, (const float*)nullptr, (const float*)nullptr);
     RGA3_CHECK_LAUNCH("bce_dice_grad");
     return 0;
@@ -683,7 +661,7 @@ extern "C" int rga3_bce_dice_grad(const float* logits, const float* targets, con
 extern "C" int rga3_bce_dice_grad_dev(const float* logits, const float* targets, const float* sums4, float* dlogits, int64_t n_masks, int64_t hw,
                                       const float* coef_bce_dev, const float* coef_dice_dev, void* stream) {
     RGA3_CHECK_ARG(logits && targets && sums4 && dlogits && coef_bce_dev && coef_dice_dev && n_masks > 0 && hw > 0, "bce_dice_grad_dev: bad args");
-    hipLaunchKernelGGL(bce_dice_grad_kernel, dim3(gd(n_masks * hw)), dim3(256), 0, (hipStream_t)stream, logits, targets, sums4, dlogits, (long)n_masks,
+    hipLaunchKernelGGL(bce_dice_grad_kernel, dim3(grid1d(n_masks * hw)), dim3(256), 0, (hipStream_t)stream, logits, targets, sums4, dlogits, (long)n_masks,
                        (long)hw, 1.f, 1.f, coef_bce_dev, coef_dice_dev);
     RGA3_CHECK_LAUNCH("bce_dice_grad_dev");
     return 0;

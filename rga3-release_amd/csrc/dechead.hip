@@ -26,8 +26,6 @@ struct Mlp3 {
 };
 struct Mlp3Batch { Mlp3 m[MLP3_MAX]; };
 
-__device__ __forceinline__ float bf16_round(float v) { return bf2f(f2bf(v)); }
-
 // yout[j] = act(bf16(sum_i W[j][i] xin[i] + bias[j])) for j < n_out; xin / yout bf16 rows in LDS (a layer's output IS bf16: nothing is lost between layers).
 // The row is the B operand of 16x16x32 MFMAs (every column of the tile carries the same row; column 0 is kept), 16 weight rows the A operand, read straight from L2:
 // a wave instruction touches 16 rows x 64 contiguous bytes and a wave keeps all 8 k-steps of a 16-row tile in flight.  History: a lane per output column walking

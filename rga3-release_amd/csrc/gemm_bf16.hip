@@ -19,8 +19,8 @@
 //  * 1-D grid with a bijective XCD remap + grouped tile order so neighbouring tiles share an L2.
 #include "common.h"
 #include "act_table.h"
+#include "loop_tags.h"
 #include <cstdlib>
-#include <type_traits>
 #include <utility>
 
 namespace rga3 {
@@ -836,10 +836,6 @@ __global__ __launch_bounds__(512) void gemm_nt_pp_kernel(GemmArgs p) {
                 __builtin_amdgcn_global_load_lds((gbl_void*)(base + soff[kind][i]), (lds_void*)(dst + i * second), 16, 0, 0);
         }
     };
-    using K_A0 = std::integral_constant<int, 0>;
-    using K_A1 = std::integral_constant<int, 1>;
-    using K_B0 = std::integral_constant<int, 2>;
-    using K_B1 = std::integral_constant<int, 3>;
     // wait until at most n half-tiles (2 loads each) issued by this lane are still in flight
     auto wait_halftiles = [&](int n) {
         if (n >= 4) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
@@ -890,8 +886,6 @@ __global__ __launch_bounds__(512) void gemm_nt_pp_kernel(GemmArgs p) {
         __builtin_amdgcn_s_setprio(0);
         __builtin_amdgcn_s_barrier();
     };
-    using H0 = std::integral_constant<int, 0>;
-    using H1 = std::integral_constant<int, 1>;
 
     // ---- prologue: S[0..5] = tile 0 complete + A0, B0 of tile 1
     stage(K_A0{}, 0, 0);
@@ -1167,10 +1161,6 @@ __global__ __launch_bounds__(512) void gemm_nt_sk_kernel(GemmArgs p, SkArgs sk) 
         asm volatile("" : "+v"(o));
         __builtin_amdgcn_global_load_lds((gbl_void*)(base + o), (lds_void*)(smem + buf * BUF + wid * 1024), 16, 0, 0);
     };
-    using K_A0 = std::integral_constant<int, 0>;
-    using K_A1 = std::integral_constant<int, 1>;
-    using K_B0 = std::integral_constant<int, 2>;
-    using K_B1 = std::integral_constant<int, 3>;
     auto wait_halftiles = [&](int n) {
         if (n >= 4) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
         else if (n == 3) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
@@ -1253,8 +1243,6 @@ __global__ __launch_bounds__(512) void gemm_nt_sk_kernel(GemmArgs p, SkArgs sk) 
         __builtin_amdgcn_s_setprio(0);
         __builtin_amdgcn_s_barrier();
     };
-    using H0 = std::integral_constant<int, 0>;
-    using H1 = std::integral_constant<int, 1>;
     // ---- MH == 3 (192-row tiles): THREE phases of 16 MFMAs per K-tile instead of four of 12.  The fixed cost of a phase (two barriers, the fragment reads, the DMA
     //      issue: ~170 cycles against 512 of matrix work for the two waves of a SIMD) is what made the four-phase form of these tiles lose the 8 % of padding they save
     //      at M = 2112 = 11 x 192 (520 vs 523 us on the gate | up product).  Phase u multiplies m-tiles 2u, 2u + 1 of the wave's 96 rows by ALL four n-tiles: the B
@@ -1282,9 +1270,6 @@ __global__ __launch_bounds__(512) void gemm_nt_sk_kernel(GemmArgs p, SkArgs sk) 
         __builtin_amdgcn_s_setprio(0);
         __builtin_amdgcn_s_barrier();
     };
-    using U0 = std::integral_constant<int, 0>;
-    using U1 = std::integral_constant<int, 1>;
-    using U2 = std::integral_constant<int, 2>;
 
     // activation table (GELU / SwiGLU epilogues): 10 KiB behind the two buffers, once per workgroup = once per CU and launch
     if constexpr (act_uses_table<ACT>()) stage_act_table<8>(smem + 2 * BUF, ACT == ACT_SWIGLU, wid, lane);
@@ -1705,10 +1690,6 @@ __global__ __launch_bounds__(256) void gemm_nt_w4_kernel(GemmArgs p) {
         asm volatile("" : "+v"(o));
         __builtin_amdgcn_global_load_lds((gbl_void*)(base + o), (lds_void*)(smem + buf * BUF + kind * HALF + (wid + 4 * i) * 1024), 16, 0, 0);
     };
-    using K_A0 = std::integral_constant<int, 0>;
-    using K_A1 = std::integral_constant<int, 1>;
-    using K_B0 = std::integral_constant<int, 2>;
-    using K_B1 = std::integral_constant<int, 3>;
     auto stage_all = [&](auto KIND, int kt, int buf) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) stage_piece(KIND, i, kt, buf);
@@ -1775,10 +1756,6 @@ __global__ __launch_bounds__(256) void gemm_nt_w4_kernel(GemmArgs p) {
                     ++s;
                 }
     };
-    using H0 = std::integral_constant<int, 0>;
-    using H1 = std::integral_constant<int, 1>;
-    using TRUE_T = std::true_type;
-    using FALSE_T = std::false_type;
 
     // One K-tile in buffer PARITY: TWO barriers.  X (start): [B1 A1](q) have landed, every wave has retired its reads of [A0 B0](q) -- their regions take [A0 B0](q+2)
     // during Q0 / Q1.  Y (middle): [A0 B0](q+1) have landed, the reads of [B1 A1](q) are retired -- their regions take [B1 A1](q+2) during Q2 / Q3.  In front of either
@@ -2050,20 +2027,10 @@ static int launch_sk(const GemmArgs& a0, bool split, hipStream_t st, bool ragged
     static_assert(LDS <= 160 * 1024, "persistent kernel: LDS");
     if constexpr (MH == 4) {
         if (sk.ragged) {
-            auto kern = gemm_nt_sk_kernel<ACT, OUT_F32, 4, true>;
-            static LdsGrant lds_grant_rg;
-            if (int rc = grant_dyn_lds((const void*)kern, LDS, lds_grant_rg, "gemm")) return rc;
-            hipLaunchKernelGGL(kern, dim3((unsigned)sk.P), dim3(512), LDS, st, a, sk);
-            RGA3_CHECK_LAUNCH("gemm_nt_sk_kernel<ragged>");
-            return 0;
+            return launch_lds<gemm_nt_sk_kernel<ACT, OUT_F32, 4, true>>(dim3((unsigned)sk.P), dim3(512), LDS, st, "gemm_nt_sk_kernel<ragged>", a, sk);
         }
     }
-    auto kern = gemm_nt_sk_kernel<ACT, OUT_F32, MH>;
-    static LdsGrant lds_grant;
-    if (int rc = grant_dyn_lds((const void*)kern, LDS, lds_grant, "gemm")) return rc;
-    hipLaunchKernelGGL(kern, dim3((unsigned)sk.P), dim3(512), LDS, st, a, sk);
-    RGA3_CHECK_LAUNCH("gemm_nt_sk_kernel");
-    return 0;
+    return launch_lds<gemm_nt_sk_kernel<ACT, OUT_F32, MH>>(dim3((unsigned)sk.P), dim3(512), LDS, st, "gemm_nt_sk_kernel", a, sk);
 }
 
 // tile 25: falls back to the persistent kernel when the product does not have few tiles and a long K
@@ -2087,11 +2054,7 @@ static int launch_splitk(const GemmArgs& a0, hipStream_t st) {
     if (sk.P > kSkMaxP) return launch_sk<ACT, OUT_F32>(a0, false, st);
     sk_plan_uniform(sk, nk);
     constexpr int LDS = 2 * 4 * 128 * 128;
-    auto kern = gemm_nt_sk_kernel<ACT_NONE, false>;
-    static LdsGrant lds_grant;
-    if (int rc = grant_dyn_lds((const void*)kern, LDS, lds_grant, "gemm")) return rc;
-    hipLaunchKernelGGL(kern, dim3((unsigned)sk.P), dim3(512), LDS, st, a, sk);
-    RGA3_CHECK_LAUNCH("gemm_nt_sk_kernel<split-K>");
+    if (int rc = launch_lds<gemm_nt_sk_kernel<ACT_NONE, false>>(dim3((unsigned)sk.P), dim3(512), LDS, st, "gemm_nt_sk_kernel<split-K>", a, sk)) return rc;
     SlabReduceArgs r;
     r.slabs = ws.slabs; r.C = a.C; r.bias = a.bias; r.M = a.M; r.N = a.N; r.ntm = a.ntm; r.ntn = a.ntn; r.group_m = a.group_m; r.S = S;
     r.out_f32 = OUT_F32 ? 1 : 0; r.ldc = a.ldc;
@@ -2110,12 +2073,7 @@ static int launch_pp(const GemmArgs& a0, hipStream_t st) {
     constexpr int LDS_RES = pp_res_lds<ACT, OUT_F32>() ? 8 * 1024 + 8 * (N192 ? res_stage_bytes<4, 96>() : res_stage_bytes<8, 64>()) : 0;
     constexpr int LDS = LDS_MAIN > LDS_RES ? LDS_MAIN : LDS_RES;
     static_assert(LDS <= 160 * 1024, "ping-pong kernel: LDS");
-    auto kern = gemm_nt_pp_kernel<ACT, OUT_F32, LNF, N192>;
-    static LdsGrant lds_grant;
-    if (int rc = grant_dyn_lds((const void*)kern, LDS, lds_grant, "gemm")) return rc;
-    hipLaunchKernelGGL(kern, dim3((unsigned)(a.ntm * a.ntn)), dim3(512), LDS, st, a);
-    RGA3_CHECK_LAUNCH("gemm_nt_pp_kernel");
-    return 0;
+    return launch_lds<gemm_nt_pp_kernel<ACT, OUT_F32, LNF, N192>>(dim3((unsigned)(a.ntm * a.ntn)), dim3(512), LDS, st, "gemm_nt_pp_kernel", a);
 }
 
 template <int ACT, bool OUT_F32>
@@ -2126,12 +2084,7 @@ static int launch_w4(const GemmArgs& a0, hipStream_t st) {
     a.ntn = (int)cdiv(a.N, 256);
     a.group_m = pick_group_m(a.ntm, 256);
     constexpr int LDS = 2 * 4 * 128 * 128 + (act_uses_table<ACT>() ? kActTabBytes : 0);
-    auto kern = gemm_nt_w4_kernel<ACT, OUT_F32>;
-    static LdsGrant lds_grant;
-    if (int rc = grant_dyn_lds((const void*)kern, LDS, lds_grant, "gemm")) return rc;
-    hipLaunchKernelGGL(kern, dim3((unsigned)(a.ntm * a.ntn)), dim3(256), LDS, st, a);
-    RGA3_CHECK_LAUNCH("gemm_nt_w4_kernel");
-    return 0;
+    return launch_lds<gemm_nt_w4_kernel<ACT, OUT_F32>>(dim3((unsigned)(a.ntm * a.ntn)), dim3(256), LDS, st, "gemm_nt_w4_kernel", a);
 }
 
 template <int BM, int BN, int WM, int WN, int ACT, bool OUT_F32, int PIPE, int LNF = 0>
@@ -2143,13 +2096,7 @@ static int launch_cfg(const GemmArgs& a0, hipStream_t st) {
     constexpr int STAGE = (BM + BN) * 128;
     constexpr int LDS = (PIPE == 3 ? 3 : 2) * STAGE;
     static_assert(LDS <= 160 * 1024, "tile does not fit the CU's LDS");
-    auto kern = gemm_nt_kernel<BM, BN, WM, WN, ACT, OUT_F32, PIPE, LNF>;
-    static LdsGrant lds_grant;
-    if (int rc = grant_dyn_lds((const void*)kern, LDS, lds_grant, "gemm")) return rc;
-    dim3 grid((unsigned)(a.ntm * a.ntn));
-    hipLaunchKernelGGL(kern, grid, dim3(64 * WM * WN), LDS, st, a);
-    RGA3_CHECK_LAUNCH("gemm_nt_kernel");
-    return 0;
+    return launch_lds<gemm_nt_kernel<BM, BN, WM, WN, ACT, OUT_F32, PIPE, LNF>>(dim3((unsigned)(a.ntm * a.ntn)), dim3(64 * WM * WN), LDS, st, "gemm_nt_kernel", a);
 }
 
 __global__ __launch_bounds__(256) void tn_slab_sum_kernel(const float* __restrict__ slabs, void* __restrict__ out, long n, long ldc, int ncols, int Z, int out_f32);
@@ -2178,11 +2125,7 @@ static int launch_split64(const GemmArgs& a0, hipStream_t st) {
     a.C = ws.slabs;
     a.ldc = a.N;
     constexpr int LDS = 2 * (64 + 64) * 128;
-    auto kern = gemm_nt_kernel<64, 64, 2, 2, ACT_NONE, true, 0>;
-    static LdsGrant lds_grant;
-    if (int rc = grant_dyn_lds((const void*)kern, LDS, lds_grant, "gemm")) return rc;
-    hipLaunchKernelGGL(kern, dim3((unsigned)tiles, (unsigned)S), dim3(256), LDS, st, a);
-    RGA3_CHECK_LAUNCH("gemm_nt_kernel<split 64>");
+    if (int rc = launch_lds<gemm_nt_kernel<64, 64, 2, 2, ACT_NONE, true, 0>>(dim3((unsigned)tiles, (unsigned)S), dim3(256), LDS, st, "gemm_nt_kernel<split 64>", a)) return rc;
     const long n = (long)a0.M * a0.N;
     hipLaunchKernelGGL(tn_slab_sum_kernel, dim3((unsigned)cdiv(n / 4, 256)), dim3(256), 0, st, (const float*)ws.slabs, a0.C, n, (long)a0.ldc, (int)a0.N, (int)S, OUT_F32 ? 1 : 0);
     RGA3_CHECK_LAUNCH("tn_slab_sum_kernel");

@@ -9,8 +9,7 @@
 // every byte that moves through LDS carries twice the FLOPs.  Both operands read their 32 K-bytes per lane the same way
 // (bytes [32 (lane>>4), +32) of row lane&15), so whatever order the instruction assigns to those bytes inside K is the same for A and B.
 #include "common.h"
-
-#include <type_traits>
+#include "loop_tags.h"
 
 namespace rga3 {
 
@@ -147,10 +146,6 @@ __global__ __launch_bounds__(512) void gemm_fp8_pp_kernel(Fp8GemmArgs p) {
         for (int i = 0; i < 2; ++i)
             __builtin_amdgcn_global_load_lds((gbl_void*)(base + soff[kind][i]), (lds_void*)(dst + i * 8192), 16, 0, 0);
     };
-    using K_A0 = std::integral_constant<int, 0>;
-    using K_A1 = std::integral_constant<int, 1>;
-    using K_B0 = std::integral_constant<int, 2>;
-    using K_B1 = std::integral_constant<int, 3>;
     auto wait_halftiles = [&](int n) {
         if (n >= 4) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
         else if (n == 3) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
@@ -208,8 +203,6 @@ __global__ __launch_bounds__(512) void gemm_fp8_pp_kernel(Fp8GemmArgs p) {
         __builtin_amdgcn_s_setprio(0);
         __builtin_amdgcn_s_barrier();
     };
-    using H0 = std::integral_constant<int, 0>;
-    using H1 = std::integral_constant<int, 1>;
 
     stage(K_A0{}, 0, 0);
     stage(K_B0{}, 0, 0);
@@ -327,14 +320,6 @@ __global__ __launch_bounds__(512) void gemm_fp8_pp_kernel(Fp8GemmArgs p) {
 //      is written as bf16 and read back by quant_fp8_rows_kernel (3 x 2 bytes per element of traffic); fused, only the e4m3 bytes + one scale per row
 //      leave the kernel.  One workgroup per row, two passes over the (L2-resident) inputs: amax of the bf16-ROUNDED values, then the same values quantised
 //      -- bit-identical to swiglu_{fwd,bwd}_kernel followed by quant_fp8_rows_kernel.
-__device__ __forceinline__ void unpack8f(const u32x4& v, float* f) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        f[2 * i] = __uint_as_float(v[i] << 16);
-        f[2 * i + 1] = __uint_as_float(v[i] & 0xffff0000u);
-    }
-}
-__device__ __forceinline__ float bfround(float x) { return __uint_as_float(((unsigned)f2bf(x)) << 16); }
 __device__ __forceinline__ u32x2 quant8(const float* f, float scale) {
     const float r = 1.0f / scale;
     int lo = 0, hi = 0;
@@ -364,10 +349,10 @@ __global__ __launch_bounds__(256) void swiglu_fwd_quant_kernel(const unsigned sh
     auto values = [&](int ch, float* o) {   // swiglu_fwd_kernel's arithmetic, result rounded to bf16 as its store does
         float g[8], u[8];
         const long goff = (long)(ch / 2) * 32 + (ch % 2) * 8;
-        unpack8f(*(const u32x4*)(gr + goff), g);
-        unpack8f(*(const u32x4*)(gr + goff + 16), u);
+        unpack8(*(const u32x4*)(gr + goff), g);
+        unpack8(*(const u32x4*)(gr + goff + 16), u);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = bfround(swiglu_fwd_elem(g[e], u[e]));
+        for (int e = 0; e < 8; ++e) o[e] = bf16_round(swiglu_fwd_elem(g[e], u[e]));
     };
     // The row is walked ONCE: a thread's first KEEP chunks stay in registers as packed bf16 (the amax pass rounds them anyway) and are quantised from there --
     // the second evaluation of silu (exp + reciprocal per element) was 105 of this kernel's 125 us at I = 18 944.  Chunks beyond KEEP (I > 20 480) are recomputed.
@@ -401,7 +386,7 @@ __global__ __launch_bounds__(256) void swiglu_fwd_quant_kernel(const unsigned sh
         const int ch = threadIdx.x + i * 256;
         if (ch < nch) {
             float o[8];
-            unpack8f(kept[i], o);
+            unpack8(kept[i], o);
             *(u32x2*)(q + t * I + ch * 8) = quant8(o, scale);
         }
     }
@@ -422,14 +407,14 @@ __global__ __launch_bounds__(256) void swiglu_bwd_quant_kernel(const unsigned sh
     auto values = [&](int ch, float* dg, float* du) {   // swiglu_bwd_kernel's arithmetic, rounded to bf16 as its stores do
         float g[8], u[8], d[8];
         const long goff = (long)(ch / 2) * 32 + (ch % 2) * 8;
-        unpack8f(*(const u32x4*)(gr + goff), g);
-        unpack8f(*(const u32x4*)(gr + goff + 16), u);
-        unpack8f(*(const u32x4*)(dr + ch * 8), d);
+        unpack8(*(const u32x4*)(gr + goff), g);
+        unpack8(*(const u32x4*)(gr + goff + 16), u);
+        unpack8(*(const u32x4*)(dr + ch * 8), d);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             swiglu_bwd_elem(g[e], u[e], d[e], dg[e], du[e]);
-            dg[e] = bfround(dg[e]);
-            du[e] = bfround(du[e]);
+            dg[e] = bf16_round(dg[e]);
+            du[e] = bf16_round(du[e]);
         }
     };
     constexpr int KEEP = 10;   // (as in the forward twin: one evaluation per element, kept as packed bf16)
@@ -466,8 +451,8 @@ __global__ __launch_bounds__(256) void swiglu_bwd_quant_kernel(const unsigned sh
         const int ch = threadIdx.x + i * 256;
         if (ch < nch) {
             float dg[8], du[8];
-            unpack8f(kg[i], dg);
-            unpack8f(ku[i], du);
+            unpack8(kg[i], dg);
+            unpack8(ku[i], du);
             const long goff = (long)(ch / 2) * 32 + (ch % 2) * 8;
             *(u32x2*)(q + t * 2 * I + goff) = quant8(dg, scale);
             *(u32x2*)(q + t * 2 * I + goff + 16) = quant8(du, scale);
@@ -511,11 +496,7 @@ extern "C" int rga3_gemm_fp8(const void* Aq, const void* Wq, const float* sa, co
     a.ntn = (int)cdiv(N, 256);
     a.group_m = a.ntm <= 16 ? a.ntm : 4;
     constexpr int LDS = 2 * 4 * 128 * 128;
-    static LdsGrant lds_grant;
-    if (int rc = grant_dyn_lds((const void*)gemm_fp8_pp_kernel, LDS, lds_grant, "gemm_fp8")) return rc;
-    hipLaunchKernelGGL(gemm_fp8_pp_kernel, dim3((unsigned)(a.ntm * a.ntn)), dim3(512), LDS, (hipStream_t)stream, a);
-    RGA3_CHECK_LAUNCH("gemm_fp8_pp_kernel");
-    return 0;
+    return launch_lds<gemm_fp8_pp_kernel>(dim3((unsigned)(a.ntm * a.ntn)), dim3(512), LDS, (hipStream_t)stream, "gemm_fp8_pp_kernel", a);
 }
 
 extern "C" int rga3_swiglu_fwd_quant_fp8(const void* gu, void* q, float* scales, int64_t T, int64_t I, void* stream) {

@@ -484,12 +484,7 @@ __global__ __launch_bounds__(hm288::NT) void hiera_mlp288_kernel(Hm288Args p) {
 
 template <class K>
 static int launch_hiera_mlp(const HmArgs& a, hipStream_t st, const char* name) {
-    auto kern = hiera_mlp_kernel<K>;
-    static LdsGrant lds_grant;
-    if (int rc = grant_dyn_lds((const void*)kern, K::LDS, lds_grant, name)) return rc;
-    hipLaunchKernelGGL(kern, dim3((unsigned)cdiv(a.M, K::TOK)), dim3(K::NT), K::LDS, st, a);
-    RGA3_CHECK_LAUNCH(name);
-    return 0;
+    return launch_lds<hiera_mlp_kernel<K>>(dim3((unsigned)cdiv(a.M, K::TOK)), dim3(K::NT), K::LDS, st, name, a);
 }
 
 }  // namespace rga3
@@ -550,11 +545,7 @@ extern "C" int rga3_hiera_mlp288(const void* x, const void* pack, const void* b2
     RGA3_CHECK_ARG(x && pack && b2 && y && M > 0, "hiera_mlp288: null pointer / M %ld", (long)M);
     RGA3_CHECK_ARG((((uintptr_t)x | (uintptr_t)pack | (uintptr_t)y) & 15) == 0 && (((uintptr_t)b2) & 7) == 0, "hiera_mlp288: alignment");
     RGA3_CHECK_ARG(x != y, "hiera_mlp288: in place is not supported (the residual is re-read)");
-    static LdsGrant lds_grant;
-    if (int rc = grant_dyn_lds((const void*)hiera_mlp288_kernel, hm288::LDS, lds_grant, "hiera_mlp288")) return rc;
     Hm288Args a;
     a.x = (const unsigned short*)x; a.pack = (const char*)pack; a.b2 = (const unsigned short*)b2; a.y = (unsigned short*)y; a.M = M; a.eps = eps;
-    hipLaunchKernelGGL(hiera_mlp288_kernel, dim3((unsigned)cdiv(M, hm288::TOK)), dim3(hm288::NT), hm288::LDS, (hipStream_t)stream, a);
-    RGA3_CHECK_LAUNCH("hiera_mlp288_kernel");
-    return 0;
+    return launch_lds<hiera_mlp288_kernel>(dim3((unsigned)cdiv(M, hm288::TOK)), dim3(hm288::NT), hm288::LDS, (hipStream_t)stream, "hiera_mlp288_kernel", a);
 }

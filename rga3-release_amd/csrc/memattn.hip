@@ -274,9 +274,6 @@ static int memattn_launch(const void* q, const void* k, const void* m, void* out
                    "%s: strides", name);
     RGA3_CHECK_ARG(scale > 0.f, "%s: scale must be positive", name);
     RGA3_CHECK_ARG((((uintptr_t)q | (uintptr_t)k | (uintptr_t)m | (uintptr_t)ws) & 15) == 0, "%s: 16-byte alignment", name);
-    auto kern = memattn_cross_kernel<DM, NW>;
-    static LdsGrant lds_grant;
-    if (int rc = grant_dyn_lds((const void*)kern, MaGeom<DM>::LDS, lds_grant, name)) return rc;
     MemAttnArgs a;
     a.q = (const unsigned short*)q; a.k = (const unsigned short*)k; a.m = (const unsigned short*)m; a.out = (unsigned short*)out;
     a.part_o = ws; a.part_ml = ws + (int64_t)nsplit * Nq * DM;
@@ -285,8 +282,7 @@ static int memattn_launch(const void* q, const void* k, const void* m, void* out
     a.scale_log2 = scale * 1.4426950408889634f;
     hipStream_t st = (hipStream_t)stream;
     const unsigned nqb = (unsigned)cdiv(Nq, 32 * NW);
-    hipLaunchKernelGGL(kern, dim3(nqb * (unsigned)nsplit), dim3(64 * NW), MaGeom<DM>::LDS, st, a);
-    RGA3_CHECK_LAUNCH(name);
+    if (int rc = launch_lds<memattn_cross_kernel<DM, NW>>(dim3(nqb * (unsigned)nsplit), dim3(64 * NW), MaGeom<DM>::LDS, st, name, a)) return rc;
     if (!out) return 0;
     hipLaunchKernelGGL(memattn_combine_kernel<DM>, dim3((unsigned)cdiv(Nq, 4)), dim3(256), 0, st, a);
     RGA3_CHECK_LAUNCH(name);

@@ -4,20 +4,6 @@
 
 namespace rga3 {
 
-__device__ __forceinline__ void unpack8(const u32x4& v, float* f) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        f[2 * i] = __uint_as_float(v[i] << 16);
-        f[2 * i + 1] = __uint_as_float(v[i] & 0xffff0000u);
-    }
-}
-__device__ __forceinline__ u32x4 pack8(const float* f) {
-    u32x4 v;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = pack_bf2(f[2 * i], f[2 * i + 1]);
-    return v;
-}
-
 // ------------------------------------------------------------------------------------------------ RMSNorm
 // one wave per row; the row stays in registers between the statistics pass and the scale pass.
 template <int MAXC>
@@ -500,12 +486,6 @@ __global__ __launch_bounds__(256) void ce_rows_kernel(const void* __restrict__ l
     }
 }
 
-static inline unsigned grid_for(long total, int per_block = 256, long cap = 256L * 8 * 4) {
-    long b = cdiv(total, per_block);
-    if (b < 1) b = 1;
-    return (unsigned)(b > cap ? cap : b);
-}
-
 }  // namespace rga3
 
 using namespace rga3;
@@ -612,7 +592,7 @@ extern "C" int rga3_gather_rows(const void* table, const int64_t* idx, void* out
     RGA3_CHECK_ARG(table && idx && out, "gather_rows: null pointer");
     RGA3_CHECK_ARG(n_idx > 0 && rows_per_idx > 0 && dim > 0 && dim % 8 == 0 && ld_table % 8 == 0 && ld_out % 8 == 0, "gather_rows: bad shape");
     const long total = n_idx * rows_per_idx * (dim / 8);
-    hipLaunchKernelGGL(move_rows_kernel<false>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)table,
+    hipLaunchKernelGGL(move_rows_kernel<false>, dim3(grid1d(total)), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)table,
                        (const long*)idx, (unsigned short*)out, (long)n_idx, (long)rows_per_idx, (int)dim, (long)ld_table, (long)ld_out);
     RGA3_CHECK_LAUNCH("gather_rows");
     return 0;
@@ -623,7 +603,7 @@ extern "C" int rga3_scatter_rows(const void* src, const int64_t* idx, void* out,
     RGA3_CHECK_ARG(src && idx && out, "scatter_rows: null pointer");
     RGA3_CHECK_ARG(n_idx > 0 && rows_per_idx > 0 && dim > 0 && dim % 8 == 0 && ld_src % 8 == 0 && ld_out % 8 == 0, "scatter_rows: bad shape");
     const long total = n_idx * rows_per_idx * (dim / 8);
-    hipLaunchKernelGGL(move_rows_kernel<true>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)src,
+    hipLaunchKernelGGL(move_rows_kernel<true>, dim3(grid1d(total)), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)src,
                        (const long*)idx, (unsigned short*)out, (long)n_idx, (long)rows_per_idx, (int)dim, (long)ld_src, (long)ld_out);
     RGA3_CHECK_LAUNCH("scatter_rows");
     return 0;
@@ -632,7 +612,7 @@ extern "C" int rga3_scatter_rows(const void* src, const int64_t* idx, void* out,
 extern "C" int rga3_pad_cols(const void* src, void* dst, int64_t rows, int64_t cols, int64_t ld_src, int64_t ld_dst, void* stream) {
     RGA3_CHECK_ARG(src && dst, "pad_cols: null pointer");
     RGA3_CHECK_ARG(rows > 0 && cols > 0 && ld_dst >= cols && ld_dst % 8 == 0, "pad_cols: bad shape");
-    hipLaunchKernelGGL(pad_cols_kernel, dim3(grid_for(rows * (ld_dst / 8))), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)src,
+    hipLaunchKernelGGL(pad_cols_kernel, dim3(grid1d(rows * (ld_dst / 8))), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)src,
                        (unsigned short*)dst, (long)rows, (int)cols, (long)ld_src, (long)ld_dst);
     RGA3_CHECK_LAUNCH("pad_cols");
     return 0;
@@ -640,7 +620,7 @@ extern "C" int rga3_pad_cols(const void* src, void* dst, int64_t rows, int64_t c
 
 extern "C" int rga3_silu_mul(const void* a, const void* b, void* out, int64_t n, void* stream) {
     RGA3_CHECK_ARG(a && b && out && n > 0, "silu_mul: bad args");
-    hipLaunchKernelGGL(ew2_kernel<0>, dim3(grid_for(n / 8 + 1)), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)a,
+    hipLaunchKernelGGL(ew2_kernel<0>, dim3(grid1d(n / 8 + 1)), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)a,
                        (const unsigned short*)b, (unsigned short*)out, (long)n);
     RGA3_CHECK_LAUNCH("silu_mul");
     return 0;
@@ -648,7 +628,7 @@ extern "C" int rga3_silu_mul(const void* a, const void* b, void* out, int64_t n,
 
 extern "C" int rga3_add(const void* a, const void* b, void* out, int64_t n, void* stream) {
     RGA3_CHECK_ARG(a && b && out && n > 0, "add: bad args");
-    hipLaunchKernelGGL(ew2_kernel<1>, dim3(grid_for(n / 8 + 1)), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)a,
+    hipLaunchKernelGGL(ew2_kernel<1>, dim3(grid1d(n / 8 + 1)), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)a,
                        (const unsigned short*)b, (unsigned short*)out, (long)n);
     RGA3_CHECK_LAUNCH("add");
     return 0;

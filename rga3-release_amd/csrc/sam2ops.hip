@@ -7,20 +7,6 @@
 
 namespace rga3 {
 
-__device__ __forceinline__ void up8(const u32x4& v, float* f) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        f[2 * i] = __uint_as_float(v[i] << 16);
-        f[2 * i + 1] = __uint_as_float(v[i] & 0xffff0000u);
-    }
-}
-__device__ __forceinline__ u32x4 pk8(const float* f) {
-    u32x4 v;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = pack_bf2(f[2 * i], f[2 * i + 1]);
-    return v;
-}
-
 // ---- im2col for Conv2d(k=KS, stride=ST, pad=PD) on NCHW bf16 images -> rows [F*Ho*Wo, ldo], cols (c, kh, kw), zero tail.
 //      Thread = one 16-byte chunk of an output row (8 consecutive columns): the (c, kh, kw) decode runs once per chunk and then steps, the store is one
 //      16-byte write (the element-per-thread form wrote 2 bytes per lane with three divisions each: 585 us for 16 frames 1024^2 -> [1 M, 152]).
@@ -73,11 +59,11 @@ __global__ __launch_bounds__(256) void maxpool_win_kernel(const unsigned short* 
             for (int dx = 0; dx < 2; ++dx) {
                 const long tok = win * w * w + (2 * r + dy) * w + (2 * c + dx);
                 float f[8];
-                up8(*(const u32x4*)(x + tok * ldx + ch * 8), f);
+                unpack8(*(const u32x4*)(x + tok * ldx + ch * 8), f);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) m[e] = fmaxf(m[e], f[e]);
             }
-        *(u32x4*)(y + t * ldy + ch * 8) = pk8(m);
+        *(u32x4*)(y + t * ldy + ch * 8) = pack8(m);
     }
 }
 
@@ -93,11 +79,11 @@ __global__ __launch_bounds__(256) void upsample2x_add_kernel(const unsigned shor
         const long f = t / ((long)W * H);
         const long tb = (f * (H / 2) + y / 2) * (W / 2) + x / 2;
         float fa[8], fb[8];
-        up8(*(const u32x4*)(a + t * C + ch * 8), fa);
-        up8(*(const u32x4*)(b + tb * C + ch * 8), fb);
+        unpack8(*(const u32x4*)(a + t * C + ch * 8), fa);
+        unpack8(*(const u32x4*)(b + tb * C + ch * 8), fb);
 #pragma unroll
         for (int e = 0; e < 8; ++e) fa[e] += fb[e];
-        *(u32x4*)(o + t * C + ch * 8) = pk8(fa);
+        *(u32x4*)(o + t * C + ch * 8) = pack8(fa);
     }
 }
 
@@ -111,11 +97,11 @@ __global__ __launch_bounds__(256) void add_bcast_kernel(const unsigned short* __
         const int ch = (int)(i % nch);
         const long r = i / nch;
         float fa[8], fb[8];
-        up8(*(const u32x4*)(a + r * lda + ch * 8), fa);
-        up8(*(const u32x4*)(b + (r % rows_b) * ldb + ch * 8), fb);
+        unpack8(*(const u32x4*)(a + r * lda + ch * 8), fa);
+        unpack8(*(const u32x4*)(b + (r % rows_b) * ldb + ch * 8), fb);
 #pragma unroll
         for (int e = 0; e < 8; ++e) fa[e] += alpha * fb[e];
-        *(u32x4*)(o + r * ldo + ch * 8) = pk8(fa);
+        *(u32x4*)(o + r * ldo + ch * 8) = pack8(fa);
     }
 }
 
@@ -383,12 +369,12 @@ __global__ __launch_bounds__(512) void dwconv7_kernel(const unsigned short* __re
 #pragma unroll
         for (int kw = 0; kw < 7; ++kw) {
             float fx[8], fw[8];
-            up8(*(const u32x4*)(xin + ((ly + kh) * DW_HALO + lx + kw) * DW_CB + cg * 8), fx);
-            up8(*(const u32x4*)(taps + (kh * 7 + kw) * DW_CB + cg * 8), fw);
+            unpack8(*(const u32x4*)(xin + ((ly + kh) * DW_HALO + lx + kw) * DW_CB + cg * 8), fx);
+            unpack8(*(const u32x4*)(taps + (kh * 7 + kw) * DW_CB + cg * 8), fw);
 #pragma unroll
             for (int e = 0; e < 8; ++e) acc[e] += fx[e] * fw[e];
         }
-    *(u32x4*)(y + ((f * H + py) * (long)W + px) * C + c0 + cg * 8) = pk8(acc);
+    *(u32x4*)(y + ((f * H + py) * (long)W + px) * C + c0 + cg * 8) = pack8(acc);
 }
 
 // ---- axial complex RoPE in place (reference sam2.py:1901-1923): consecutive (even, odd) pairs, token t < n_rope uses
@@ -403,7 +389,7 @@ __global__ __launch_bounds__(256) void rope_axial_kernel(unsigned short* __restr
         const long tr = t % nq;
         float f[8];
         unsigned short* p = x + t * ldx + ch * 8;
-        up8(*(const u32x4*)p, f);
+        unpack8(*(const u32x4*)p, f);
         const float* c = cs + tr * (C / 2) + ch * 4;
         const float* s = sn + tr * (C / 2) + ch * 4;
         float o[8];
@@ -412,7 +398,7 @@ __global__ __launch_bounds__(256) void rope_axial_kernel(unsigned short* __restr
             o[2 * e] = f[2 * e] * c[e] - f[2 * e + 1] * s[e];
             o[2 * e + 1] = f[2 * e] * s[e] + f[2 * e + 1] * c[e];
         }
-        *(u32x4*)p = pk8(o);
+        *(u32x4*)p = pack8(o);
     }
 }
 
@@ -430,14 +416,14 @@ __global__ __launch_bounds__(256) void pixel_shuffle_kernel(const unsigned short
         const long src = (f * H + Y / 2) * (long)W + X / 2;
         const int q = (Y & 1) * 2 + (X & 1);
         float fg[8], fb[8];
-        up8(*(const u32x4*)(g + src * (4L * Co) + q * Co + ch * 8), fg);
+        unpack8(*(const u32x4*)(g + src * (4L * Co) + q * Co + ch * 8), fg);
         if (bias) {
-            up8(*(const u32x4*)(bias + ch * 8), fb);
+            unpack8(*(const u32x4*)(bias + ch * 8), fb);
 #pragma unroll
             for (int e = 0; e < 8; ++e) fg[e] = bf2f(f2bf(fg[e] + fb[e]));
         }
         if (add) {
-            up8(*(const u32x4*)(add + t * Co + ch * 8), fb);
+            unpack8(*(const u32x4*)(add + t * Co + ch * 8), fb);
 #pragma unroll
             for (int e = 0; e < 8; ++e) fg[e] += fb[e];
         }
@@ -445,7 +431,7 @@ __global__ __launch_bounds__(256) void pixel_shuffle_kernel(const unsigned short
 #pragma unroll
             for (int e = 0; e < 8; ++e) { float tv = bf2f(f2bf(fg[e])); fg[e] = 0.5f * tv * (1.0f + erff(tv * 0.70710678118654752f)); }
         }
-        *(u32x4*)(o + t * Co + ch * 8) = pk8(fg);
+        *(u32x4*)(o + t * Co + ch * 8) = pack8(fg);
     }
 }
 
@@ -484,24 +470,16 @@ __global__ __launch_bounds__(64) void bce_dice_finish_kernel(const float* __rest
     }
 }
 
-static inline unsigned grid1(long total, long cap = 256L * 32) {
-    long b = cdiv(total, 256);
-    if (b < 1) b = 1;
-    return (unsigned)(b > cap ? cap : b);
-}
-
 }  // namespace rga3
 
 using namespace rga3;
-typedef const unsigned short* cus;
-typedef unsigned short* us;
 
 extern "C" int rga3_im2col(const void* img, void* out, int64_t F, int C, int H, int W, int ks, int stride, int pad, int64_t ld_out,
                            void* stream) {
     RGA3_CHECK_ARG(img && out && F > 0 && C > 0 && H > 0 && W > 0 && ks > 0 && stride > 0, "im2col: bad args");
     const int Ho = (H + 2 * pad - ks) / stride + 1, Wo = (W + 2 * pad - ks) / stride + 1;
     RGA3_CHECK_ARG(ld_out >= (int64_t)C * ks * ks && ld_out % 8 == 0 && (((uintptr_t)out) & 15) == 0, "im2col: ld_out too small / not a multiple of 8, or out not 16-byte aligned");
-    hipLaunchKernelGGL(im2col_kernel, dim3(grid1(F * Ho * Wo * (ld_out / 8))), dim3(256), 0, (hipStream_t)stream, (cus)img, (us)out, (int)F, C, H, W, ks,
+    hipLaunchKernelGGL(im2col_kernel, dim3(grid1d(F * Ho * Wo * (ld_out / 8))), dim3(256), 0, (hipStream_t)stream, (cus)img, (us)out, (int)F, C, H, W, ks,
                        stride, pad, Ho, Wo, (int)ld_out);
     RGA3_CHECK_LAUNCH("im2col");
     return 0;
@@ -509,7 +487,7 @@ extern "C" int rga3_im2col(const void* img, void* out, int64_t F, int C, int H, 
 
 extern "C" int rga3_maxpool2x2_win(const void* x, void* y, int64_t nwin, int w, int C, int64_t ldx, int64_t ldy, void* stream) {
     RGA3_CHECK_ARG(x && y && nwin > 0 && w >= 2 && w % 2 == 0 && C % 8 == 0 && ldx % 8 == 0 && ldy % 8 == 0, "maxpool2x2_win: bad args");
-    hipLaunchKernelGGL(maxpool_win_kernel, dim3(grid1(nwin * (w / 2) * (w / 2) * (C / 8))), dim3(256), 0, (hipStream_t)stream, (cus)x, (us)y,
+    hipLaunchKernelGGL(maxpool_win_kernel, dim3(grid1d(nwin * (w / 2) * (w / 2) * (C / 8))), dim3(256), 0, (hipStream_t)stream, (cus)x, (us)y,
                        (long)nwin, w, C, (long)ldx, (long)ldy);
     RGA3_CHECK_LAUNCH("maxpool2x2_win");
     return 0;
@@ -517,7 +495,7 @@ extern "C" int rga3_maxpool2x2_win(const void* x, void* y, int64_t nwin, int w, 
 
 extern "C" int rga3_upsample2x_add(const void* a, const void* b, void* out, int64_t F, int H, int W, int C, void* stream) {
     RGA3_CHECK_ARG(a && b && out && F > 0 && H % 2 == 0 && W % 2 == 0 && C % 8 == 0, "upsample2x_add: bad args");
-    hipLaunchKernelGGL(upsample2x_add_kernel, dim3(grid1(F * H * W * (C / 8))), dim3(256), 0, (hipStream_t)stream, (cus)a, (cus)b, (us)out, (long)F, H, W, C);
+    hipLaunchKernelGGL(upsample2x_add_kernel, dim3(grid1d(F * H * W * (C / 8))), dim3(256), 0, (hipStream_t)stream, (cus)a, (cus)b, (us)out, (long)F, H, W, C);
     RGA3_CHECK_LAUNCH("upsample2x_add");
     return 0;
 }
@@ -525,7 +503,7 @@ extern "C" int rga3_upsample2x_add(const void* a, const void* b, void* out, int6
 extern "C" int rga3_add_bcast(const void* a, const void* b, void* out, int64_t rows, int64_t rows_b, int C, int64_t lda, int64_t ldb,
                               int64_t ldo, float alpha, void* stream) {
     RGA3_CHECK_ARG(a && b && out && rows > 0 && rows_b > 0 && C % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0 && ldo % 8 == 0, "add_bcast: bad args");
-    hipLaunchKernelGGL(add_bcast_kernel, dim3(grid1(rows * (C / 8))), dim3(256), 0, (hipStream_t)stream, (cus)a, (cus)b, (us)out, (long)rows,
+    hipLaunchKernelGGL(add_bcast_kernel, dim3(grid1d(rows * (C / 8))), dim3(256), 0, (hipStream_t)stream, (cus)a, (cus)b, (us)out, (long)rows,
                        (long)rows_b, C, (long)lda, (long)ldb, (long)ldo, alpha);
     RGA3_CHECK_LAUNCH("add_bcast");
     return 0;
@@ -535,7 +513,7 @@ extern "C" int rga3_bilinear(const void* in, int in_dtype, float* out, const int
                              void* stream) {
     RGA3_CHECK_ARG(in && out && N > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0, "bilinear: bad args");
     RGA3_CHECK_ARG(in_dtype == RGA3_BF16 || in_dtype == RGA3_F32, "bilinear: dtype");
-    dim3 g(grid1(N * Ho * Wo));
+    dim3 g(grid1d(N * Ho * Wo));
     if (in_dtype == RGA3_BF16)
         hipLaunchKernelGGL(bilinear_kernel<true>, g, dim3(256), 0, (hipStream_t)stream, in, out, plane_idx, (long)N, Hi, Wi, Ho, Wo);
     else
@@ -547,7 +525,7 @@ extern "C" int rga3_bilinear(const void* in, int in_dtype, float* out, const int
 extern "C" int rga3_conv3x3s2(const void* x, int x_dtype, const void* w, const void* bias, void* y, int64_t F, int H, int W, int Cin, int Cout,
                               float sig_scale, float sig_bias, void* stream) {
     RGA3_CHECK_ARG(x && w && y && F > 0 && H % 2 == 0 && W % 2 == 0 && Cin > 0 && Cout > 0, "conv3x3s2: bad args");
-    dim3 g(grid1(F * (H / 2) * (W / 2) * Cout));
+    dim3 g(grid1d(F * (H / 2) * (W / 2) * Cout));
     if (x_dtype == RGA3_F32)
         hipLaunchKernelGGL(conv3x3s2_kernel<true>, g, dim3(256), 0, (hipStream_t)stream, x, (cus)w, (cus)bias, (us)y, (long)F, H, W, Cin, Cout, sig_scale, sig_bias);
     else
@@ -564,7 +542,7 @@ extern "C" int rga3_conv3x3s2_ln_gelu(const void* x, int x_dtype, const void* w,
     RGA3_CHECK_ARG((x_dtype == RGA3_F32 && Cin == 1 && Cout == 4) || (x_dtype == RGA3_BF16 && Cin == 4 && Cout == 16),
                    "conv3x3s2_ln_gelu: (Cin, Cout) = (%d, %d): (1, 4) from an f32 plane or (4, 16) from bf16", Cin, Cout);
     RGA3_CHECK_ARG((((uintptr_t)x | (uintptr_t)y) & 15) == 0, "conv3x3s2_ln_gelu: 16-byte alignment");
-    dim3 g(grid1(F * (H / 2) * (W / 2)));
+    dim3 g(grid1d(F * (H / 2) * (W / 2)));
     hipStream_t st = (hipStream_t)stream;
     if (Cin == 1)
         hipLaunchKernelGGL((conv3x3s2_ln_gelu_kernel<1, 4, true>), g, dim3(256), 0, st, x, (cus)w, (cus)bias, (cus)ln_w, (cus)ln_b, eps, (us)y, (long)F, H, W, sig_scale, sig_bias);
@@ -597,7 +575,7 @@ extern "C" int rga3_copy_many(void* const* dst, const void* const* src, const in
 
 extern "C" int rga3_im2col3x3s2(const void* x, void* cols, int64_t F, int H, int W, int C, void* stream) {
     RGA3_CHECK_ARG(x && cols && F > 0 && H % 2 == 0 && W % 2 == 0 && C > 0 && C % 8 == 0, "im2col3x3s2: bad args");
-    hipLaunchKernelGGL(im2col3x3s2_kernel, dim3(grid1(F * (H / 2) * (W / 2) * 9L * (C / 8))), dim3(256), 0, (hipStream_t)stream, (cus)x, (us)cols, (long)F, H, W, C);
+    hipLaunchKernelGGL(im2col3x3s2_kernel, dim3(grid1d(F * (H / 2) * (W / 2) * 9L * (C / 8))), dim3(256), 0, (hipStream_t)stream, (cus)x, (us)cols, (long)F, H, W, C);
     RGA3_CHECK_LAUNCH("im2col3x3s2");
     return 0;
 }
@@ -615,14 +593,14 @@ extern "C" int rga3_dwconv7x7(const void* x, const void* w, const void* bias, vo
 extern "C" int rga3_rope_axial_inplace(void* x, const float* cos, const float* sin, int64_t n_rope, int nq, int C, int64_t ldx, void* stream) {
     RGA3_CHECK_ARG(x && cos && sin && nq > 0 && C % 8 == 0 && ldx % 8 == 0, "rope_axial: bad args");
     if (n_rope <= 0) return 0;
-    hipLaunchKernelGGL(rope_axial_kernel, dim3(grid1(n_rope * (C / 8))), dim3(256), 0, (hipStream_t)stream, (us)x, cos, sin, (long)n_rope, nq, C, (long)ldx);
+    hipLaunchKernelGGL(rope_axial_kernel, dim3(grid1d(n_rope * (C / 8))), dim3(256), 0, (hipStream_t)stream, (us)x, cos, sin, (long)n_rope, nq, C, (long)ldx);
     RGA3_CHECK_LAUNCH("rope_axial");
     return 0;
 }
 
 extern "C" int rga3_pixel_shuffle2x(const void* g, const void* bias, const void* add, void* out, int64_t F, int H, int W, int Co, int act, void* stream) {
     RGA3_CHECK_ARG(g && out && F > 0 && Co % 8 == 0, "pixel_shuffle2x: bad args");
-    hipLaunchKernelGGL(pixel_shuffle_kernel, dim3(grid1(F * 4L * H * W * (Co / 8))), dim3(256), 0, (hipStream_t)stream, (cus)g, (cus)bias, (cus)add, (us)out,
+    hipLaunchKernelGGL(pixel_shuffle_kernel, dim3(grid1d(F * 4L * H * W * (Co / 8))), dim3(256), 0, (hipStream_t)stream, (cus)g, (cus)bias, (cus)add, (us)out,
                        (long)F, H, W, Co, act);
     RGA3_CHECK_LAUNCH("pixel_shuffle2x");
     return 0;

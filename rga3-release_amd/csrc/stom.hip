@@ -412,12 +412,8 @@ extern "C" int rga3_stom_flow(const float* tracks, const void* visibility, int* 
     int p = 2;
     while (p < n_points) p <<= 1;
     const int lds = p * (int)sizeof(u32);
-    static LdsGrant lds_grant;
-    if (int rc = grant_dyn_lds((const void*)stom_flow_kernel, lds, lds_grant, "stom_flow")) return rc;
-    hipLaunchKernelGGL(stom_flow_kernel, dim3((unsigned)frames), dim3(kFlowThreads), lds, (hipStream_t)stream, tracks, (const u8*)visibility, records, (int)n_points, p,
-                       vip_frame_idx);
-    RGA3_CHECK_LAUNCH("stom_flow");
-    return 0;
+    return launch_lds<stom_flow_kernel>(dim3((unsigned)frames), dim3(kFlowThreads), lds, (hipStream_t)stream, "stom_flow", tracks, (const u8*)visibility, records,
+                                        (int)n_points, p, vip_frame_idx);
 }
 
 extern "C" int rga3_stom_shift_composite(const void* frames_u8, const void* overlay_rgba, const int* records, void* out, int64_t frames, int64_t h, int64_t w,

@@ -5,20 +5,6 @@
 
 namespace rga3 {
 
-__device__ __forceinline__ void un8(const u32x4& v, float* f) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        f[2 * i] = __uint_as_float(v[i] << 16);
-        f[2 * i + 1] = __uint_as_float(v[i] & 0xffff0000u);
-    }
-}
-__device__ __forceinline__ u32x4 pk8_(const float* f) {
-    u32x4 v;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = pack_bf2(f[2 * i], f[2 * i + 1]);
-    return v;
-}
-
 // dx = r * g - x * r^3 * mean(g * x) (+ add), g = dy * w, r = rsqrt(mean(x^2) + eps); one wave per row.
 template <int MAXC>
 __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const unsigned short* __restrict__ x, const unsigned short* __restrict__ w,
@@ -36,16 +22,16 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const unsigned short* 
         if (ch < nch) {
             float fx[8], fd[8], fw[8];
             xb[i] = *(const u32x4*)(x + row * dim + ch * 8);
-            un8(xb[i], fx);
-            un8(*(const u32x4*)(dy + row * dim + ch * 8), fd);
-            un8(*(const u32x4*)(w + ch * 8), fw);
+            unpack8(xb[i], fx);
+            unpack8(*(const u32x4*)(dy + row * dim + ch * 8), fd);
+            unpack8(*(const u32x4*)(w + ch * 8), fw);
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 fd[e] *= fw[e];
                 ss += fx[e] * fx[e];
                 sg += fd[e] * fx[e];
             }
-            gb[i] = pk8_(fd);
+            gb[i] = pack8(fd);
         }
     }
     ss = wave_sum(ss);
@@ -57,12 +43,12 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const unsigned short* 
         const int ch = lane + i * 64;
         if (ch < nch) {
             float fx[8], fg[8], fa[8];
-            un8(xb[i], fx);
-            un8(gb[i], fg);
-            if (add) un8(*(const u32x4*)(add + row * dim + ch * 8), fa);
+            unpack8(xb[i], fx);
+            unpack8(gb[i], fg);
+            if (add) unpack8(*(const u32x4*)(add + row * dim + ch * 8), fa);
 #pragma unroll
             for (int e = 0; e < 8; ++e) fg[e] = r * fg[e] - fx[e] * coef + (add ? fa[e] : 0.f);
-            *(u32x4*)(dx + row * dim + ch * 8) = pk8_(fg);
+            *(u32x4*)(dx + row * dim + ch * 8) = pack8(fg);
         }
     }
 }
@@ -85,9 +71,9 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_block_kernel(const unsigned s
         const int ch = threadIdx.x + i * 256;
         if (ch < nch) {
             float fw[8];
-            un8(*(const u32x4*)(x + row * dim + ch * 8), fx[i]);
-            un8(*(const u32x4*)(dy + row * dim + ch * 8), fg[i]);
-            un8(*(const u32x4*)(w + ch * 8), fw);
+            unpack8(*(const u32x4*)(x + row * dim + ch * 8), fx[i]);
+            unpack8(*(const u32x4*)(dy + row * dim + ch * 8), fg[i]);
+            unpack8(*(const u32x4*)(w + ch * 8), fw);
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 fg[i][e] *= fw[e];
@@ -109,10 +95,10 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_block_kernel(const unsigned s
         const int ch = threadIdx.x + i * 256;
         if (ch < nch) {
             float fa[8], o[8];
-            if (add) un8(*(const u32x4*)(add + row * dim + ch * 8), fa);
+            if (add) unpack8(*(const u32x4*)(add + row * dim + ch * 8), fa);
 #pragma unroll
             for (int e = 0; e < 8; ++e) o[e] = r * fg[i][e] - fx[i][e] * coef + (add ? fa[e] : 0.f);
-            *(u32x4*)(dx + row * dim + ch * 8) = pk8_(o);
+            *(u32x4*)(dx + row * dim + ch * 8) = pack8(o);
         }
     }
 }
@@ -127,13 +113,13 @@ __global__ __launch_bounds__(256) void swiglu_bwd_kernel(const unsigned short* _
         const long blk = ch / 2, half = ch % 2;
         const long goff = t * 2 * I + blk * 32 + half * 8;
         float g[8], u[8], d[8], dg[8], du[8];
-        un8(*(const u32x4*)(gu + goff), g);
-        un8(*(const u32x4*)(gu + goff + 16), u);
-        un8(*(const u32x4*)(da + t * I + ch * 8), d);
+        unpack8(*(const u32x4*)(gu + goff), g);
+        unpack8(*(const u32x4*)(gu + goff + 16), u);
+        unpack8(*(const u32x4*)(da + t * I + ch * 8), d);
 #pragma unroll
         for (int e = 0; e < 8; ++e) swiglu_bwd_elem(g[e], u[e], d[e], dg[e], du[e]);
-        *(u32x4*)(dgu + goff) = pk8_(dg);
-        *(u32x4*)(dgu + goff + 16) = pk8_(du);
+        *(u32x4*)(dgu + goff) = pack8(dg);
+        *(u32x4*)(dgu + goff + 16) = pack8(du);
     }
 }
 
@@ -147,11 +133,11 @@ __global__ __launch_bounds__(256) void swiglu_fwd_kernel(const unsigned short* _
         const long blk = ch / 2, half = ch % 2;
         const long goff = t * 2 * I + blk * 32 + half * 8;
         float g[8], u[8], o[8];
-        un8(*(const u32x4*)(gu + goff), g);
-        un8(*(const u32x4*)(gu + goff + 16), u);
+        unpack8(*(const u32x4*)(gu + goff), g);
+        unpack8(*(const u32x4*)(gu + goff + 16), u);
 #pragma unroll
         for (int e = 0; e < 8; ++e) o[e] = swiglu_fwd_elem(g[e], u[e]);
-        *(u32x4*)(a + t * I + ch * 8) = pk8_(o);
+        *(u32x4*)(a + t * I + ch * 8) = pack8(o);
     }
 }
 
@@ -209,11 +195,11 @@ __global__ __launch_bounds__(256) void segment_sum_rows_kernel(const unsigned sh
         float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         for (long j = a; j < b; ++j) {
             float f[8];
-            un8(*(const u32x4*)(x + rows[j] * ldx + ch * 8), f);
+            unpack8(*(const u32x4*)(x + rows[j] * ldx + ch * 8), f);
 #pragma unroll
             for (int e = 0; e < 8; ++e) acc[e] += f[e];
         }
-        *(u32x4*)(out + u * dim + ch * 8) = pk8_(acc);
+        *(u32x4*)(out + u * dim + ch * 8) = pack8(acc);
     }
 }
 
@@ -256,7 +242,7 @@ __global__ __launch_bounds__(256) void sumsq_partials_kernel(const unsigned shor
     const long n8 = n / 8;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n8; i += (long)gridDim.x * 256) {
         float f[8];
-        un8(*(const u32x4*)(g + i * 8), f);
+        unpack8(*(const u32x4*)(g + i * 8), f);
 #pragma unroll
         for (int e = 0; e < 8; ++e) s += f[e] * f[e];
     }
@@ -297,7 +283,7 @@ __global__ __launch_bounds__(256) void adamw8_kernel(unsigned short* __restrict_
         // rows whose gradient AND both moments are exactly zero (never touched) are left alone: with weight decay 0 their update is exactly zero
         if (row_active && !row_active[i / row_len8]) continue;
         float gr[8], w[8], mi[8], vi[8];
-        un8(*(const u32x4*)(g + i * 8), gr);
+        unpack8(*(const u32x4*)(g + i * 8), gr);
         *(f32x4*)(w) = *(const f32x4*)(master + i * 8);     *(f32x4*)(w + 4) = *(const f32x4*)(master + i * 8 + 4);
         *(f32x4*)(mi) = *(const f32x4*)(m + i * 8);         *(f32x4*)(mi + 4) = *(const f32x4*)(m + i * 8 + 4);
         *(f32x4*)(vi) = *(const f32x4*)(v + i * 8);         *(f32x4*)(vi + 4) = *(const f32x4*)(v + i * 8 + 4);
@@ -311,7 +297,7 @@ __global__ __launch_bounds__(256) void adamw8_kernel(unsigned short* __restrict_
         *(f32x4*)(master + i * 8) = *(f32x4*)(w);           *(f32x4*)(master + i * 8 + 4) = *(f32x4*)(w + 4);
         *(f32x4*)(m + i * 8) = *(f32x4*)(mi);               *(f32x4*)(m + i * 8 + 4) = *(f32x4*)(mi + 4);
         *(f32x4*)(v + i * 8) = *(f32x4*)(vi);               *(f32x4*)(v + i * 8 + 4) = *(f32x4*)(vi + 4);
-        *(u32x4*)(p + i * 8) = pk8_(w);
+        *(u32x4*)(p + i * 8) = pack8(w);
     }
     if (blockIdx.x == 0 && threadIdx.x < (n & 7)) {   // ragged tail, scalar
         const long i = n8 * 8 + threadIdx.x;
@@ -331,18 +317,12 @@ __global__ __launch_bounds__(256) void scatter_add_rows_kernel(unsigned short* _
         const int ch = (int)(t % nch);
         float a[8], b[8];
         unsigned short* d = dst + idx[r] * ld_dst + ch * 8;
-        un8(*(const u32x4*)d, a);
-        un8(*(const u32x4*)(src + r * ld_src + ch * 8), b);
+        unpack8(*(const u32x4*)d, a);
+        unpack8(*(const u32x4*)(src + r * ld_src + ch * 8), b);
 #pragma unroll
         for (int e = 0; e < 8; ++e) a[e] += scale * b[e];
-        *(u32x4*)d = pk8_(a);
+        *(u32x4*)d = pack8(a);
     }
-}
-
-static inline unsigned g1(long total, long cap = 256L * 32) {
-    long b = cdiv(total, 256);
-    if (b < 1) b = 1;
-    return (unsigned)(b > cap ? cap : b);
 }
 
 // ------------------------------------------------------------------------------------------------ dropout (LoRA branch)
@@ -411,8 +391,6 @@ __global__ __launch_bounds__(256) void dropout_pair_kernel(const unsigned short*
 }  // namespace rga3
 
 using namespace rga3;
-typedef const unsigned short* cus;
-typedef unsigned short* us;
 
 extern "C" int rga3_rmsnorm_bwd(const void* x, const void* weight, const void* dy, const void* add, void* dx, int64_t rows, int64_t dim,
                                 float eps, void* stream) {
@@ -463,14 +441,14 @@ extern "C" int rga3_dropout_pair_bf16(const void* xa, const void* xb, void* ya, 
 
 extern "C" int rga3_swiglu_bwd(const void* gu, const void* da, void* dgu, int64_t T, int64_t I, void* stream) {
     RGA3_CHECK_ARG(gu && da && dgu && T > 0 && I > 0 && I % 16 == 0, "swiglu_bwd: bad args");
-    hipLaunchKernelGGL(swiglu_bwd_kernel, dim3(g1(T * (I / 8))), dim3(256), 0, (hipStream_t)stream, (cus)gu, (cus)da, (us)dgu, (long)T, (long)I);
+    hipLaunchKernelGGL(swiglu_bwd_kernel, dim3(grid1d(T * (I / 8))), dim3(256), 0, (hipStream_t)stream, (cus)gu, (cus)da, (us)dgu, (long)T, (long)I);
     RGA3_CHECK_LAUNCH("swiglu_bwd");
     return 0;
 }
 
 extern "C" int rga3_swiglu_fwd(const void* gu, void* a, int64_t T, int64_t I, void* stream) {
     RGA3_CHECK_ARG(gu && a && T > 0 && I > 0 && I % 16 == 0, "swiglu_fwd: bad args");
-    hipLaunchKernelGGL(swiglu_fwd_kernel, dim3(g1(T * (I / 8))), dim3(256), 0, (hipStream_t)stream, (cus)gu, (us)a, (long)T, (long)I);
+    hipLaunchKernelGGL(swiglu_fwd_kernel, dim3(grid1d(T * (I / 8))), dim3(256), 0, (hipStream_t)stream, (cus)gu, (us)a, (long)T, (long)I);
     RGA3_CHECK_LAUNCH("swiglu_fwd");
     return 0;
 }
@@ -517,7 +495,7 @@ extern "C" int rga3_adamw_step(void* param, float* master, const void* grad, flo
                                float eps, float weight_decay, int step, float grad_scale, void* stream) {
     RGA3_CHECK_ARG(param && master && grad && m && v && n > 0 && step >= 1, "adamw_step: bad args");
     const float bc1 = 1.f - powf(beta1, (float)step), bc2 = 1.f - powf(beta2, (float)step);
-    hipLaunchKernelGGL(adamw_kernel, dim3(g1(n)), dim3(256), 0, (hipStream_t)stream, (us)param, master, (cus)grad, m, v, (long)n, lr, beta1, beta2, eps,
+    hipLaunchKernelGGL(adamw_kernel, dim3(grid1d(n)), dim3(256), 0, (hipStream_t)stream, (us)param, master, (cus)grad, m, v, (long)n, lr, beta1, beta2, eps,
                        weight_decay, bc1, bc2, grad_scale);
     RGA3_CHECK_LAUNCH("adamw_step");
     return 0;
@@ -525,7 +503,7 @@ extern "C" int rga3_adamw_step(void* param, float* master, const void* grad, flo
 
 extern "C" int rga3_sumsq_accum(const void* g, float* out, int64_t n, void* stream) {
     RGA3_CHECK_ARG(g && out && n > 0, "sumsq_accum: bad args");
-    hipLaunchKernelGGL(sumsq_kernel, dim3(g1(n, 2048)), dim3(256), 0, (hipStream_t)stream, (cus)g, out, (long)n);
+    hipLaunchKernelGGL(sumsq_kernel, dim3(grid1d(n, 256, 2048)), dim3(256), 0, (hipStream_t)stream, (cus)g, out, (long)n);
     RGA3_CHECK_LAUNCH("sumsq_accum");
     return 0;
 }
@@ -549,7 +527,7 @@ extern "C" int rga3_adamw_step_clip(void* param, float* master, const void* grad
     RGA3_CHECK_ARG(param && master && grad && m && v && n > 0 && step >= 1, "adamw_step_clip: bad args");
     RGA3_CHECK_ARG((((uintptr_t)param | (uintptr_t)grad | (uintptr_t)master | (uintptr_t)m | (uintptr_t)v) & 15) == 0, "adamw_step_clip: pointers must be 16-byte aligned");
     const float bc1 = 1.f - powf(beta1, (float)step), bc2 = 1.f - powf(beta2, (float)step);
-    hipLaunchKernelGGL(adamw8_kernel, dim3(g1(cdiv(n, 8), 256L * 16)), dim3(256), 0, (hipStream_t)stream, (us)param, master, (cus)grad, m, v, (long)n, lr, beta1, beta2,
+    hipLaunchKernelGGL(adamw8_kernel, dim3(grid1d(cdiv(n, 8), 256, 256L * 16)), dim3(256), 0, (hipStream_t)stream, (us)param, master, (cus)grad, m, v, (long)n, lr, beta1, beta2,
                        eps, weight_decay, bc1, bc2, sumsq, max_norm, (const unsigned char*)nullptr, 1L);
     RGA3_CHECK_LAUNCH("adamw_step_clip");
     return 0;
@@ -564,7 +542,7 @@ extern "C" int rga3_adamw_step_clip_rows(void* param, float* master, const void*
     RGA3_CHECK_ARG((((uintptr_t)param | (uintptr_t)grad | (uintptr_t)master | (uintptr_t)m | (uintptr_t)v) & 15) == 0, "adamw_step_clip_rows: pointers must be 16-byte aligned");
     const float bc1 = 1.f - powf(beta1, (float)step), bc2 = 1.f - powf(beta2, (float)step);
     const int64_t n = rows * row_len;
-    hipLaunchKernelGGL(adamw8_kernel, dim3(g1(cdiv(n, 8), 256L * 16)), dim3(256), 0, (hipStream_t)stream, (us)param, master, (cus)grad, m, v, (long)n, lr, beta1, beta2,
+    hipLaunchKernelGGL(adamw8_kernel, dim3(grid1d(cdiv(n, 8), 256, 256L * 16)), dim3(256), 0, (hipStream_t)stream, (us)param, master, (cus)grad, m, v, (long)n, lr, beta1, beta2,
                        eps, 0.f, bc1, bc2, sumsq, max_norm, row_active, (long)(row_len / 8));
     RGA3_CHECK_LAUNCH("adamw_step_clip_rows");
     return 0;
@@ -573,7 +551,7 @@ extern "C" int rga3_adamw_step_clip_rows(void* param, float* master, const void*
 extern "C" int rga3_scatter_add_rows(void* dst, const int64_t* idx, const void* src, int64_t n, int64_t dim, int64_t ld_dst, int64_t ld_src, float scale,
                                      void* stream) {
     RGA3_CHECK_ARG(dst && idx && src && n > 0 && dim > 0 && dim % 8 == 0 && ld_dst % 8 == 0 && ld_src % 8 == 0, "scatter_add_rows: bad args");
-    hipLaunchKernelGGL(scatter_add_rows_kernel, dim3(g1(n * (dim / 8))), dim3(256), 0, (hipStream_t)stream, (us)dst, (const long*)idx, (cus)src, (long)n, (int)dim,
+    hipLaunchKernelGGL(scatter_add_rows_kernel, dim3(grid1d(n * (dim / 8))), dim3(256), 0, (hipStream_t)stream, (us)dst, (const long*)idx, (cus)src, (long)n, (int)dim,
                        (long)ld_dst, (long)ld_src, scale);
     RGA3_CHECK_LAUNCH("scatter_add_rows");
     return 0;

@@ -769,6 +769,67 @@ def test_attn_five_of_six_output_tiles_is_the_same_bits(dev, D, T, seg):
     assert float((lse.float().cpu() - rlse).abs().max()) < 2e-2
 
 
+_LDS_GRANT_CHILD = r"""
+import sys
+sys.path[:0] = [%r, %r]
+import torch
+from oracle import kernels_ref as R
+from rga3.hip import ops
+
+dev = torch.device("cuda:0")
+def rel_l2(a, b):
+    a, b = a.float().cpu(), b.float().cpu()
+    return ((a - b).norm() / (b.norm() + 1e-12)).item()
+def rand(shape, seed):
+    g = torch.Generator().manual_seed(seed)
+    return torch.randn(shape, generator=g).to(torch.bfloat16).to(dev)
+
+D, H = 72, 2
+scale = D ** -0.5
+cu_q = torch.tensor([0, 64, 128], dtype=torch.int32)
+q = rand((128, H, D), 5) * 0.8
+for lk in (64, 192, 256):   # window kernel LDS: 18 688 B (no grant), 55 552 B (first grant), 73 984 B (a larger one)
+    k, v = rand((2 * lk, H, D), 6 + lk) * 0.8, rand((2 * lk, H, D), 7 + lk) * 0.8
+    cu_k = torch.tensor([0, lk, 2 * lk], dtype=torch.int32)
+    out = ops.attn_varlen(q, k, v, cu_q.to(dev), cu_k.to(dev), 64, scale, causal=False, max_k=lk)
+    old = ops.attn_varlen(q, k, v, cu_q.to(dev), cu_k.to(dev), 64, scale, causal=False, max_k=lk, impl=2)
+    ref, _ = R.attn_varlen_ref(q.cpu(), k.cpu(), v.cpu(), cu_q, cu_k, scale, False)
+    e_old, e_ref = rel_l2(out, old), rel_l2(out, ref)
+    print("window lk", lk, "vs pipelined", e_old, "vs oracle", e_ref)
+    assert e_old < 4e-3 and e_ref < 8e-3, lk
+
+D, Hq, Hkv, T = 128, 4, 2, 320   # the 8-wave backward kernels, causal
+scale = D ** -0.5
+cu = torch.tensor([0, T], dtype=torch.int32)
+q, k, v, do = rand((T, Hq, D), 1), rand((T, Hkv, D), 2), rand((T, Hkv, D), 3), rand((T, Hq, D), 4)
+o, lse = ops.attn_varlen(q, k, v, cu.to(dev), cu.to(dev), T, scale, True, return_lse=True)
+dq, dk, dv = ops.attn_varlen_bwd(q, k, v, o, do, lse, cu.to(dev), cu.to(dev), T, T, scale, True)
+qf, kf, vf = (t.float().cpu().requires_grad_(True) for t in (q, k, v))
+ref, _ = R.attn_varlen_ref(qf, kf, vf, cu, cu, scale, True)
+ref.backward(do.float().cpu())
+errs = rel_l2(dq, qf.grad), rel_l2(dk, kf.grad), rel_l2(dv, vf.grad)
+print("bwd dq dk dv", *errs)
+assert max(errs) < 2e-2
+print("ok")
+"""
+
+
+def test_dynamic_lds_grant_grows_between_calls(dev):
+    """The dynamic-LDS grant of a kernel whose need GROWS after a grant was made (launch_lds in csrc/common.h): in a fresh process -- no earlier test has granted the
+    maximum -- the window kernel at D = 72 runs on key segments of 64, 192 and 256 (18 688 B: nothing to grant; 55 552 B: the first grant; 73 984 B: a larger one),
+    each against the pipelined kernel (impl=2) and the softmax oracle at the bounds of test_attn_window_kernel; then one causal backward at D = 128 (the 8-wave
+    kernels) against the oracle's autograd at the bound of test_attention_backward.  A grant that did not grow makes the launch fail (Rga3Error), not fault."""
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = _LDS_GRANT_CHILD % (root, os.path.join(root, "rga3-release_amd"))
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=120)
+    print(r.stdout)
+    assert r.returncode == 0 and r.stdout.rstrip().endswith("ok"), (r.stdout + r.stderr)[-3000:]
+
+
 def test_attn_forced_rescale(dev):
     """Spike one key so the running max jumps at a later tile (exercises the alpha rescale path)."""
     from rga3.hip import ops
