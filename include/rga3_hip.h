@@ -13,6 +13,9 @@
  *  - return 0 on success, a negative code otherwise (-hipError_t for runtime errors, RGA3_EINVAL for
  *    argument errors); the message is retrievable with rga3_last_error() (thread-local).
  *  - bf16 tensors are passed as raw 16-bit words; "ld*" / strides are in ELEMENTS.
+ *  - a view must hold its rows: a leading dimension or token / head / frame stride shorter than the row it addresses is
+ *    refused (RGA3_EINVAL) before any launch, except for a single row, for an operand that is not passed, and for the
+ *    head-major [heads][tokens][D] attention layouts, whose head stride spans the tokens.
  */
 #ifndef RGA3_HIP_H
 #define RGA3_HIP_H

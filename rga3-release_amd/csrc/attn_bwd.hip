@@ -521,6 +521,13 @@ extern "C" int rga3_attn_varlen_bwd(const void* q, const void* k, const void* v,
     RGA3_CHECK_ARG(D >= 8 && D <= 128 && D % 8 == 0, "attn_bwd: head dim %d unsupported (multiple of 8, <= 128)", D);
     for (int i = 0; i < 16; ++i) RGA3_CHECK_ARG(strides16[i] % 4 == 0, "attn_bwd: stride %d must be a multiple of 4 elements", i);
     for (int i = 0; i < 10; ++i) RGA3_CHECK_ARG(strides16[i] % 8 == 0, "attn_bwd: input stride %d must be a multiple of 8 elements", i);
+    {
+        static const char* const names[8] = {"q", "k", "v", "o", "dout", "dq", "dk", "dv"};
+        for (int i = 0; i < 8; ++i) {
+            const bool kv = i == 1 || i == 2 || i == 6 || i == 7;
+            RGA3_CHECK_HEADS("attn_bwd", names[i], strides16[2 * i], strides16[2 * i + 1], kv ? total_k : total_q, kv ? Hkv : Hq, D);
+        }
+    }
     AttnBwdArgs a;
     a.q = (const unsigned short*)q; a.k = (const unsigned short*)k; a.v = (const unsigned short*)v; a.o = (const unsigned short*)o;
     a.dout = (const unsigned short*)dout; a.dq = (unsigned short*)dq; a.dk = (unsigned short*)dk; a.dv = (unsigned short*)dv;

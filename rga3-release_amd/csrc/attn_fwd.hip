@@ -714,6 +714,10 @@ extern "C" int rga3_attn_varlen_fwd(const void* q, const void* k, const void* v,
     RGA3_CHECK_ARG(nseg <= 65535 && Hq <= 65535, "attn: grid dims too large");
     RGA3_CHECK_ARG(k_st < (1 << 24) && v_st < (1 << 24), "attn: k/v row stride too large for 32-bit tile offsets");
     RGA3_CHECK_ARG(impl >= 0 && impl <= 31, "attn: impl %d", impl);
+    RGA3_CHECK_HEADS("attn", "q", q_st, q_sh, total_q, Hq, D);
+    RGA3_CHECK_HEADS("attn", "k", k_st, k_sh, 0, Hkv, D);
+    RGA3_CHECK_HEADS("attn", "v", v_st, v_sh, 0, Hkv, D);
+    RGA3_CHECK_HEADS("attn", "o", o_st, o_sh, total_q, Hq, D);
     const AttnImpl im = {(impl & 1) != 0, (impl & 2) != 0, (impl & 4) != 0, (impl & 8) != 0, (impl & 16) != 0};
     const bool special = !im.scalar_read && !im.wave4;   // the kernels beside the general one are open to this call
     AttnArgs a = attn_args(q, k, v, o, lse, cu_q, cu_k, total_q, Hq, Hkv, D, q_st, q_sh, k_st, k_sh, v_st, v_sh, o_st, o_sh, scale, causal);
@@ -773,6 +777,10 @@ extern "C" int rga3_attn_varlen_fwd_rope(const void* q, const void* k, const voi
     RGA3_CHECK_ARG((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)cos_q | (uintptr_t)sin_q | (uintptr_t)cos_k | (uintptr_t)sin_k) & 15) == 0 &&
                        (((uintptr_t)o) & 7) == 0, "attn_varlen_fwd_rope: pointer alignment");
     RGA3_CHECK_ARG(k_st < (1 << 24) && v_st < (1 << 24), "attn_varlen_fwd_rope: k/v row stride too large");
+    RGA3_CHECK_HEADS("attn_varlen_fwd_rope", "q", q_st, q_sh, total_q, Hq, D);
+    RGA3_CHECK_HEADS("attn_varlen_fwd_rope", "k", k_st, k_sh, 0, Hkv, D);
+    RGA3_CHECK_HEADS("attn_varlen_fwd_rope", "v", v_st, v_sh, 0, Hkv, D);
+    RGA3_CHECK_HEADS("attn_varlen_fwd_rope", "o", o_st, o_sh, total_q, Hq, D);
     RGA3_CHECK_ARG(!c32 || ((((uintptr_t)o) & 15) == 0 && o_st % 8 == 0 && o_sh % 8 == 0), "attn_varlen_fwd_rope: the causal D = 128 rows write 16-byte pieces: o must be 16-byte aligned, strides multiples of 8");
     AttnArgs a = attn_args(q, k, v, o, lse, cu_q, cu_k, total_q, Hq, Hkv, D, q_st, q_sh, k_st, k_sh, v_st, v_sh, o_st, o_sh, scale, causal);
     a.rope_cos = cos_q; a.rope_sin = sin_q; a.rope_kcos = cos_k; a.rope_ksin = sin_k;

@@ -535,7 +535,8 @@ extern "C" int rga3_layernorm_bwd(const void* x, const void* weight, const void*
 }
 
 extern "C" int rga3_colsum_accum(const void* x, float* out, int64_t rows, int64_t cols, int64_t ld, void* stream) {
-    RGA3_CHECK_ARG(x && out && rows > 0 && cols > 0 && ld >= cols, "colsum_accum: bad args");
+    RGA3_CHECK_ARG(x && out && rows > 0 && cols > 0, "colsum_accum: bad args");
+    RGA3_CHECK_LD("colsum_accum", "ld", ld, cols, 2);
     const int rpw = 256;
     RGA3_CHECK_ARG(cdiv(rows, rpw) <= 65535, "colsum_accum: too many rows");
     hipLaunchKernelGGL(colsum_kernel, dim3((unsigned)cdiv(cols, 256), (unsigned)cdiv(rows, rpw)), dim3(256), 0, (hipStream_t)stream, (cus)x, out, (long)rows,
@@ -565,7 +566,8 @@ extern "C" int64_t rga3_colsum_ws_floats(int64_t rows, int64_t cols) {
 
 // out[c] = sum_r x[r, c], written (not accumulated), deterministic; cols % 8 == 0, ld % 8 == 0, x 16-byte aligned; ws: rga3_colsum_ws_floats() f32 elements
 extern "C" int rga3_colsum(const void* x, float* out, int64_t rows, int64_t cols, int64_t ld, float* ws, int64_t ws_floats, void* counters, void* stream) {
-    RGA3_CHECK_ARG(x && out && ws && rows > 0 && cols > 0 && ld >= cols, "colsum: bad args");
+    RGA3_CHECK_ARG(x && out && ws && rows > 0 && cols > 0, "colsum: bad args");
+    RGA3_CHECK_LD("colsum", "ld", ld, cols, 2);
     RGA3_CHECK_ARG(cols % 8 == 0 && ld % 8 == 0 && (((uintptr_t)x) & 15) == 0, "colsum: cols / ld multiples of 8 and 16-byte aligned rows (use rga3_colsum_accum otherwise)");
     int CG, RS, nchunk;
     long rpw;

@@ -162,6 +162,8 @@ extern "C" int rga3_mlp3_rows(const void* const* ptrs, const int64_t* dims, int 
         RGA3_CHECK_ARG(m.in > 0 && m.hid > 0 && m.out > 0 && m.in % 8 == 0 && m.hid % 8 == 0 && m.in <= MLP3_MAXDIM && m.hid <= MLP3_MAXDIM && m.out <= MLP3_MAXDIM,
                        "mlp3_rows: dims %d -> %d -> %d (inputs multiples of 8, all <= 512)", m.in, m.hid, m.out);
         RGA3_CHECK_ARG((((uintptr_t)m.w0 | (uintptr_t)m.w1 | (uintptr_t)m.w2) & 15) == 0, "mlp3_rows: weights must be 16-byte aligned");
+        RGA3_CHECK_LD("mlp3_rows", "x frame stride", m.x_bstride, m.in, B);
+        RGA3_CHECK_LD("mlp3_rows", "y frame stride", m.y_bstride, m.out, B);
     }
     // 16 waves: a 256-wide layer is one 16-row tile per wave, so a layer costs one L2 round trip instead of four in a row
     hipLaunchKernelGGL(mlp3_rows_kernel, dim3((unsigned)n, (unsigned)B), dim3(1024), 0, (hipStream_t)stream, P);
@@ -172,7 +174,8 @@ extern "C" int rga3_mlp3_rows(const void* const* ptrs, const int64_t* dims, int 
 extern "C" int rga3_sam_select_objptr(const void* iou, const void* obj, const void* toks, int64_t tok_bstride, int C, const void* w0, const void* b0, const void* w1, const void* b1,
                                       const void* w2, const void* b2, const void* no_obj_ptr, int64_t* best, int32_t* sel, void* obj_ptr, int64_t B, void* stream) {
     RGA3_CHECK_ARG(iou && obj && toks && w0 && w1 && w2 && no_obj_ptr && best && sel && obj_ptr, "sam_select_objptr: null pointer");
-    RGA3_CHECK_ARG(B >= 1 && B <= 65535 && tok_bstride >= 4L * C && C > 0 && C % 8 == 0 && C <= MLP3_MAXDIM, "sam_select_objptr: B %ld C %d", (long)B, C);
+    RGA3_CHECK_ARG(B >= 1 && B <= 65535 && C > 0 && C % 8 == 0 && C <= MLP3_MAXDIM, "sam_select_objptr: B %ld C %d", (long)B, C);
+    RGA3_CHECK_LD("sam_select_objptr", "tok_bstride", tok_bstride, 4L * C, 2);
     RGA3_CHECK_ARG((((uintptr_t)w0 | (uintptr_t)w1 | (uintptr_t)w2) & 15) == 0, "sam_select_objptr: weights must be 16-byte aligned");
     SamSelectArgs a;
     a.iou = (const unsigned short*)iou; a.obj = (const unsigned short*)obj; a.toks = (const unsigned short*)toks;

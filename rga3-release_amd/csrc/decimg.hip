@@ -372,8 +372,12 @@ extern "C" int rga3_decimg_rows(const void* keys, int64_t keys_stride, const voi
                                 float scale, int64_t M, void* stream) {
     RGA3_CHECK_ARG(keys && pe && kt && vt && wq && wo && ln_w && keys_out && M > 0 && M < (1LL << 31), "decimg_rows: null pointer / M");
     RGA3_CHECK_ARG(hw >= DI_R && M % hw == 0 && nk >= 1 && nk <= DI_MAXK, "decimg_rows: hw %d, nk %d (1..16)", hw, nk);
-    RGA3_CHECK_ARG(keys_stride >= DI_D && keys_stride % 8 == 0 && pe_stride >= DI_D && pe_stride % 8 == 0 && keys_out_stride >= DI_D && keys_out_stride % 4 == 0, "decimg_rows: strides");
-    RGA3_CHECK_ARG((wk2 == nullptr) == (wv2 == nullptr) && (!wk2 || (k2 && v2 && kv_stride >= DI_I && kv_stride % 4 == 0)), "decimg_rows: next projections");
+    RGA3_CHECK_ARG(keys_stride % 8 == 0 && pe_stride % 8 == 0 && keys_out_stride % 4 == 0, "decimg_rows: keys / pe strides must be multiples of 8 elements, keys_out_stride of 4");
+    RGA3_CHECK_LD("decimg_rows", "keys_stride", keys_stride, DI_D, 2);
+    RGA3_CHECK_LD("decimg_rows", "pe_stride", pe_stride, DI_D, 2);
+    RGA3_CHECK_LD("decimg_rows", "keys_out_stride", keys_out_stride, DI_D, 2);
+    RGA3_CHECK_ARG((wk2 == nullptr) == (wv2 == nullptr) && (!wk2 || (k2 && v2 && kv_stride % 4 == 0)), "decimg_rows: next projections");
+    if (wk2) RGA3_CHECK_LD("decimg_rows", "kv_stride", kv_stride, DI_I, 2);
     RGA3_CHECK_ARG(scale > 0.f, "decimg_rows: scale");
     RGA3_CHECK_ARG((((uintptr_t)keys | (uintptr_t)pe | (uintptr_t)wq | (uintptr_t)wo | (uintptr_t)wk2 | (uintptr_t)wv2) & 15) == 0 &&
                        (((uintptr_t)kt | (uintptr_t)vt | (uintptr_t)bq | (uintptr_t)bo | (uintptr_t)ln_w | (uintptr_t)ln_b | (uintptr_t)bk2 | (uintptr_t)bv2 | (uintptr_t)keys_out |
@@ -402,8 +406,11 @@ extern "C" int rga3_attn_fewq(const void* q, int64_t q_stride, const void* k, in
                               int64_t out_stride, int frames, int nq, int nk, int H, float scale, void* stream) {
     RGA3_CHECK_ARG(q && k && vt && out && frames >= 1 && frames <= 65535 && H >= 1 && H <= 65535, "attn_fewq: null pointer / frames / heads");
     RGA3_CHECK_ARG(nq >= 1 && nq <= 16 && nk >= 1 && nk <= 16 * FQ_NW * FQ_MAXT && nk % 4 == 0, "attn_fewq: nq %d (1..16), nk %d (<= 4096, multiple of 4)", nq, nk);
-    RGA3_CHECK_ARG(q_stride % 4 == 0 && k_stride % 4 == 0 && k_head_stride % 4 == 0 && out_stride % 4 == 0 && q_stride >= 16L * H && k_stride >= 16 && out_stride >= 16L * H,
-                   "attn_fewq: strides");
+    RGA3_CHECK_ARG(q_stride % 4 == 0 && k_stride % 4 == 0 && k_head_stride % 4 == 0 && out_stride % 4 == 0, "attn_fewq: strides must be multiples of 4 elements");
+    RGA3_CHECK_LD("attn_fewq", "q_stride", q_stride, 16L * H, 2);
+    RGA3_CHECK_LD("attn_fewq", "k_stride", k_stride, 16, 2);
+    RGA3_CHECK_LD("attn_fewq", "out_stride", out_stride, 16L * H, 2);
+    RGA3_CHECK_LD("attn_fewq", "k_head_stride", k_head_stride, 16, H);
     RGA3_CHECK_ARG((((uintptr_t)q | (uintptr_t)k | (uintptr_t)vt | (uintptr_t)out) & 7) == 0 && scale > 0.f, "attn_fewq: alignment / scale");
     FewQArgs a;
     a.q = (const unsigned short*)q; a.q_st = q_stride; a.k = (const unsigned short*)k; a.k_st = k_stride; a.k_hst = k_head_stride; a.vt = (const unsigned short*)vt; a.vbias = (const unsigned short*)vbias;

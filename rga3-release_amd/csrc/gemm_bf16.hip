@@ -2756,8 +2756,12 @@ static int launch_tile(const GemmArgs& a, int tile, hipStream_t st) {
 
 // What every NT entry point checks and fills (`who` prefixes the messages); the entry point adds its own fields and bounds.
 static int nt_args(GemmArgs& a, const char* who, const void* A, const void* W, const void* bias, const void* residual, void* C, int64_t M, int64_t N, int64_t K,
-                   int64_t lda, int64_t ldw, int64_t ldc, int64_t ldr) {
+                   int64_t lda, int64_t ldw, int64_t ldc, int64_t ldr, int64_t n_out) {
     RGA3_CHECK_ARG(A && W && C, "%s: null pointer", who);
+    RGA3_CHECK_LD(who, "lda", lda, K, M);
+    RGA3_CHECK_LD(who, "ldw", ldw, K, N);
+    RGA3_CHECK_LD(who, "ldc", ldc, n_out, M);
+    if (residual) RGA3_CHECK_LD(who, "ldr", ldr, n_out, M);
     RGA3_CHECK_ARG(lda % 8 == 0 && ldw % 8 == 0, "%s: lda/ldw must be multiples of 8 elements (16-byte rows)", who);
     RGA3_CHECK_ARG((((uintptr_t)A | (uintptr_t)W | (uintptr_t)C) & 15) == 0, "%s: pointers must be 16-byte aligned", who);
     RGA3_CHECK_ARG(M * lda < (1LL << 32) && N * ldw < (1LL << 32), "%s: operands must be < 2^32 elements (32-bit staging offsets)", who);
@@ -2806,6 +2810,9 @@ extern "C" int rga3_gemm_rows16_many(const void* const* ptrs, const int64_t* dim
         RGA3_CHECK_ARG(s.act == ACT_NONE || s.act == ACT_GELU || s.act == ACT_RELU, "gemm_rows16_many: set %d: act %d", i, s.act);
         RGA3_CHECK_ARG(s.ldc >= s.N && (!s.res || s.ldr >= s.N), "gemm_rows16_many: set %d: ldc %ld / ldr %ld shorter than N %d (a residual row stride below N reads out of bounds)",
                        i, (long)s.ldc, (long)s.ldr, s.N);
+        RGA3_CHECK_LD("gemm_rows16_many", "lda", s.lda, s.K, s.M);
+        if (s.A2) RGA3_CHECK_LD("gemm_rows16_many", "lda2", s.lda2, s.K, s.M);
+        RGA3_CHECK_LD("gemm_rows16_many", "ldw", s.ldw, s.K, s.N);
         if (s.N > maxn) maxn = s.N;
     }
     hipLaunchKernelGGL(gemm_rows16_many_kernel, dim3((unsigned)cdiv(maxn, 16), (unsigned)n), dim3(64 * R16_NW), 0, (hipStream_t)stream, P);
@@ -2875,7 +2882,8 @@ static int gemm_bf16_impl(const void* A, const void* W, const void* bias, const 
                           int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldw, int64_t ldc, int64_t ldr,
                           int act, int out_dtype, int tile, void* workspace, int64_t workspace_bytes, const unsigned long long* rs_in, int64_t rs_width, float rs_eps,
                           unsigned long long* rs_out, void* stream, void* pre = nullptr, int64_t ldpre = 0) {
-    RGA3_CHECK_ARG(!pre || (act == ACT_SWIGLU && M > 4 && (((uintptr_t)pre) & 15) == 0 && ldpre >= N), "gemm: the pre-activation output goes with the SwiGLU tile epilogues (M > 4)");
+    RGA3_CHECK_ARG(!pre || (act == ACT_SWIGLU && M > 4 && (((uintptr_t)pre) & 15) == 0), "gemm: the pre-activation output goes with the SwiGLU tile epilogues (M > 4)");
+    if (pre) RGA3_CHECK_LD("gemm", "ldpre", ldpre, N, M);
     RGA3_CHECK_ARG(M > 0 && N > 0 && K > 0, "gemm: bad shape M=%ld N=%ld K=%ld", (long)M, (long)N, (long)K);
     RGA3_CHECK_ARG(K % 8 == 0, "gemm: K=%ld must be a multiple of 8 (16-byte staging chunks)", (long)K);
     RGA3_CHECK_ARG(out_dtype == RGA3_BF16 || out_dtype == RGA3_F32, "gemm: out_dtype %d", out_dtype);
@@ -2884,7 +2892,7 @@ static int gemm_bf16_impl(const void* A, const void* W, const void* bias, const 
     RGA3_CHECK_ARG(act != ACT_SWIGLU || N % 32 == 0, "gemm: swiglu needs N %% 32 == 0");
     RGA3_CHECK_ARG(find_tile(tile, E_PLAIN), "gemm: tile %d", tile);
     GemmArgs a;
-    if (int rc = nt_args(a, "gemm", A, W, bias, residual, C, M, N, K, lda, ldw, ldc, ldr)) return rc;
+    if (int rc = nt_args(a, "gemm", A, W, bias, residual, C, M, N, K, lda, ldw, ldc, ldr, act == ACT_SWIGLU ? N / 2 : N)) return rc;
     a.colscale = (const unsigned short*)colscale;
     a.ws = workspace; a.ws_bytes = workspace_bytes;
     a.rs_in = rs_in; a.rs_in_scale = rs_in ? 1.0f / (kRowSumFix * (float)rs_width) : 0.f; a.rs_eps = rs_eps; a.rs_out = rs_out;
@@ -2942,7 +2950,7 @@ extern "C" int rga3_gemm_lnsum_bf16(const void* A, const void* W, const void* bi
     const Tile* t = find_tile(tile, E_LNSUM);
     RGA3_CHECK_ARG(t, "gemm_lnsum: tile %d", tile);
     GemmArgs a;
-    if (int rc = nt_args(a, "gemm_lnsum", A, W, bias, residual, C, M, N, K, lda, ldw, ldc, ldr)) return rc;
+    if (int rc = nt_args(a, "gemm_lnsum", A, W, bias, residual, C, M, N, K, lda, ldw, ldc, ldr, N)) return rc;
     a.ln_parts = row_parts;
     return launch_tile<ACT_NONE, false, 2>(a, t->id, (hipStream_t)stream);
 }
@@ -2977,7 +2985,9 @@ extern "C" int rga3_gemm_cat_bf16(const void* A, const void* W, const void* bias
     RGA3_CHECK_ARG(t, "gemm_cat: tile %d", tile);
     RGA3_CHECK_ARG(!Wn || N % t->bn == 0, "gemm_cat: with an N side, N = %ld must be a multiple of the tile width %d", (long)N, t->bn);
     GemmArgs a;
-    if (int rc = nt_args(a, "gemm_cat", A, W, bias, nullptr, C, M, N, K, lda, ldw, ldc, 0)) return rc;
+    if (A2) { RGA3_CHECK_LD("gemm_cat", "lda2", lda2, K2, M); RGA3_CHECK_LD("gemm_cat", "ldw2", ldw2, K2, N); }
+    if (Wn) { RGA3_CHECK_LD("gemm_cat", "ldwn", ldwn, K, N2); RGA3_CHECK_LD("gemm_cat", "ldcn", ldcn, N2, M); }
+    if (int rc = nt_args(a, "gemm_cat", A, W, bias, nullptr, C, M, N, K, lda, ldw, ldc, 0, N)) return rc;
     a.A2 = (const unsigned short*)A2; a.W2 = (const unsigned short*)W2; a.K2 = (int)K2; a.lda2 = lda2; a.ldw2 = ldw2;
     a.Wn = (const unsigned short*)Wn; a.Cn = Cn; a.N2 = (int)N2; a.ldwn = ldwn; a.ldcn = ldcn;
     return launch_tile<ACT_NONE, false, 0>(a, t->id, (hipStream_t)stream);
@@ -2995,7 +3005,7 @@ static int gemm_ln_args(GemmArgs& a, const char* who, const void* A, const void*
     RGA3_CHECK_ARG((((uintptr_t)colc) & 15) == 0 && (((uintptr_t)stats) & 7) == 0, "%s: pointer alignment", who);
     RGA3_CHECK_ARG(act == ACT_NONE || act == ACT_GELU || act == ACT_RELU, "%s: act %d", who, act);
     RGA3_CHECK_ARG(find_tile(tile, E_LN), "%s: tile %d", who, tile);
-    if (int rc = nt_args(a, who, A, Wf, bias, nullptr, C, M, N, K, lda, ldw, ldc, 0)) return rc;
+    if (int rc = nt_args(a, who, A, Wf, bias, nullptr, C, M, N, K, lda, ldw, ldc, 0, N)) return rc;
     a.colc = colc;
     return 0;
 }
@@ -3032,6 +3042,9 @@ extern "C" int rga3_gemm_tn_bf16(const void* A, const void* B, const void* bias,
     RGA3_CHECK_ARG((((uintptr_t)A | (uintptr_t)B | (uintptr_t)C | (uintptr_t)workspace) & 15) == 0, "gemm_tn: pointers must be 16-byte aligned");
     RGA3_CHECK_ARG(out_dtype == RGA3_BF16 || out_dtype == RGA3_F32, "gemm_tn: out_dtype %d", out_dtype);
     RGA3_CHECK_ARG(cdiv(M, 128) <= 65535, "gemm_tn: M too large");
+    RGA3_CHECK_LD("gemm_tn", "lda", lda, M, K);
+    RGA3_CHECK_LD("gemm_tn", "ldb", ldb, N, K);
+    RGA3_CHECK_LD("gemm_tn", "ldc", ldc, N, M);
     GemmArgs a;
     a.A = nullptr; a.W = nullptr; a.C = C;
     a.bias = (const unsigned short*)bias; a.res = nullptr; a.colscale = nullptr;
@@ -3094,6 +3107,9 @@ extern "C" int rga3_gemm_tn_many(const void* const* ptrs, const int64_t* dims, i
         RGA3_CHECK_ARG(lda % 8 == 0 && ldb % 8 == 0 && ldc % 4 == 0, "gemm_tn_many: lda/ldb must be multiples of 8 elements, ldc of 4 (product %d)", i);
         RGA3_CHECK_ARG((((uintptr_t)A | (uintptr_t)B | (uintptr_t)C) & 15) == 0, "gemm_tn_many: pointers must be 16-byte aligned (product %d)", i);
         RGA3_CHECK_ARG(out_dtype == RGA3_BF16 || out_dtype == RGA3_F32, "gemm_tn_many: out_dtype %d", out_dtype);
+        RGA3_CHECK_LD("gemm_tn_many", "lda", lda, M, K);
+        RGA3_CHECK_LD("gemm_tn_many", "ldb", ldb, N, K);
+        RGA3_CHECK_LD("gemm_tn_many", "ldc", ldc, N, M);
         GemmArgs& a = P.a[i];
         a = GemmArgs();
         a.A = nullptr; a.W = nullptr; a.bias = nullptr; a.res = nullptr; a.colscale = nullptr;

@@ -474,6 +474,8 @@ using namespace rga3;
 extern "C" int rga3_quant_fp8_rows(const void* x, void* q, float* scales, int64_t rows, int64_t K, int64_t ldx, int64_t ldq, void* stream) {
     RGA3_CHECK_ARG(x && q && scales && rows > 0 && K > 0 && K % 8 == 0 && ldx % 8 == 0 && ldq % 8 == 0, "quant_fp8_rows: rows=%ld K=%ld", (long)rows, (long)K);
     RGA3_CHECK_ARG(rows <= 0x7fffffff, "quant_fp8_rows: too many rows");
+    RGA3_CHECK_LD("quant_fp8_rows", "ldx", ldx, K, rows);
+    RGA3_CHECK_LD("quant_fp8_rows", "ldq", ldq, K, rows);
     hipLaunchKernelGGL(quant_fp8_rows_kernel, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)x, (unsigned char*)q, scales,
                        (long)rows, (int)K, (long)ldx, (long)ldq);
     RGA3_CHECK_LAUNCH("quant_fp8_rows_kernel");
@@ -487,6 +489,10 @@ extern "C" int rga3_gemm_fp8(const void* Aq, const void* Wq, const float* sa, co
     RGA3_CHECK_ARG(lda % 16 == 0 && ldw % 16 == 0, "gemm_fp8: lda/ldw must be multiples of 16 bytes");
     RGA3_CHECK_ARG((((uintptr_t)Aq | (uintptr_t)Wq | (uintptr_t)C) & 15) == 0, "gemm_fp8: pointers must be 16-byte aligned");
     RGA3_CHECK_ARG(M * lda < (1LL << 32) && N * ldw < (1LL << 32), "gemm_fp8: operands must be < 2^32 bytes (32-bit staging offsets)");
+    RGA3_CHECK_LD("gemm_fp8", "lda", lda, K, M);
+    RGA3_CHECK_LD("gemm_fp8", "ldw", ldw, K, N);
+    RGA3_CHECK_LD("gemm_fp8", "ldc", ldc, N, M);
+    if (residual) RGA3_CHECK_LD("gemm_fp8", "ldr", ldr, N, M);
     Fp8GemmArgs a;
     a.A = (const unsigned char*)Aq; a.W = (const unsigned char*)Wq; a.sa = sa; a.sw = sw;
     a.bias = (const unsigned short*)bias; a.res = (const unsigned short*)residual; a.C = (unsigned short*)C;

@@ -270,8 +270,11 @@ static int memattn_launch(const void* q, const void* k, const void* m, void* out
     RGA3_CHECK_ARG(q && k && m && ws, "%s: null pointer", name);
     RGA3_CHECK_ARG(Nq > 0 && Nk > 0 && Nq < (1 << 24) && Nk < (1 << 24), "%s: Nq %ld Nk %ld", name, (long)Nq, (long)Nk);
     RGA3_CHECK_ARG(nsplit >= 1 && nsplit <= MA_MAX_SPLIT, "%s: nsplit %d", name, nsplit);
-    RGA3_CHECK_ARG(q_stride % 8 == 0 && k_stride % 8 == 0 && m_stride % 8 == 0 && q_stride >= MA_D && k_stride >= MA_D && m_stride >= DM && (!out || out_stride >= DM),
-                   "%s: strides", name);
+    RGA3_CHECK_ARG(q_stride % 8 == 0 && k_stride % 8 == 0 && m_stride % 8 == 0, "%s: q / k / m strides must be multiples of 8 elements", name);
+    RGA3_CHECK_LD(name, "q_stride", q_stride, MA_D, 2);
+    RGA3_CHECK_LD(name, "k_stride", k_stride, MA_D, 2);
+    RGA3_CHECK_LD(name, "m_stride", m_stride, DM, 2);
+    if (out) RGA3_CHECK_LD(name, "out_stride", out_stride, DM, 2);
     RGA3_CHECK_ARG(scale > 0.f, "%s: scale must be positive", name);
     RGA3_CHECK_ARG((((uintptr_t)q | (uintptr_t)k | (uintptr_t)m | (uintptr_t)ws) & 15) == 0, "%s: 16-byte alignment", name);
     MemAttnArgs a;

@@ -315,19 +315,24 @@ extern "C" int rga3_memlayer_rows(const void* a, int64_t a_stride, int K1, const
                                   int64_t t_stride, const void* w2, const void* b2, int N2, void* y_out, int64_t y_stride, const float* cos, const float* sin,
                                   int rope_cols, int nq, int64_t M, void* stream) {
     RGA3_CHECK_ARG(res && ln_w && M > 0 && M < (1 << 30), "memlayer_rows: res / ln_w / M %ld", (long)M);
-    RGA3_CHECK_ARG(res_stride >= ML_D && res_stride % 4 == 0, "memlayer_rows: residual stride");
+    RGA3_CHECK_ARG(res_stride % 4 == 0, "memlayer_rows: res_stride must be a multiple of 4 elements");
+    RGA3_CHECK_LD("memlayer_rows", "res_stride", res_stride, ML_D, 2);
     const bool partials = part_o != nullptr;
     if (w1) {
-        RGA3_CHECK_ARG(partials ? (part_ml && nsplit >= 1 && nsplit <= 32 && K1 == 64 && !a) : (a && (K1 == 64 || K1 == 256) && a_stride >= K1 && a_stride % 8 == 0),
+        RGA3_CHECK_ARG(partials ? (part_ml && nsplit >= 1 && nsplit <= 32 && K1 == 64 && !a) : (a && (K1 == 64 || K1 == 256) && a_stride % 8 == 0),
                        "memlayer_rows: operand of product 1 (K1 %d, nsplit %d)", K1, nsplit);
+        if (a) RGA3_CHECK_LD("memlayer_rows", "a_stride", a_stride, K1, 2);
         RGA3_CHECK_ARG((((uintptr_t)w1 | (uintptr_t)a | (uintptr_t)part_o) & 15) == 0 && (((uintptr_t)b1 | (uintptr_t)part_ml) & 7) == 0, "memlayer_rows: alignment of product 1");
-        RGA3_CHECK_ARG(!x_out || (x_stride >= ML_D && x_stride % 4 == 0), "memlayer_rows: x stride");
+        RGA3_CHECK_ARG(!x_out || x_stride % 4 == 0, "memlayer_rows: x_stride must be a multiple of 4 elements");
+        if (x_out) RGA3_CHECK_LD("memlayer_rows", "x_stride", x_stride, ML_D, 2);
     } else {
         RGA3_CHECK_ARG(!a && !partials && !x_out, "memlayer_rows: operand / x_out without w1");
     }
-    RGA3_CHECK_ARG(!t_out || (t_stride >= ML_D && t_stride % 4 == 0), "memlayer_rows: t stride");
+    RGA3_CHECK_ARG(!t_out || t_stride % 4 == 0, "memlayer_rows: t_stride must be a multiple of 4 elements");
+    if (t_out) RGA3_CHECK_LD("memlayer_rows", "t_stride", t_stride, ML_D, 2);
     if (w2) {
-        RGA3_CHECK_ARG(y_out && (N2 == 256 || N2 == 768) && y_stride >= N2 && y_stride % 4 == 0, "memlayer_rows: product 2 (N2 %d)", N2);
+        RGA3_CHECK_ARG(y_out && (N2 == 256 || N2 == 768) && y_stride % 4 == 0, "memlayer_rows: product 2 (N2 %d)", N2);
+        RGA3_CHECK_LD("memlayer_rows", "y_stride", y_stride, N2, 2);
         RGA3_CHECK_ARG(rope_cols >= 0 && rope_cols <= N2 && rope_cols % 4 == 0 && (rope_cols == 0 || (cos && sin && nq > 0)), "memlayer_rows: rope (%d columns)", rope_cols);
         RGA3_CHECK_ARG((((uintptr_t)w2) & 15) == 0 && (((uintptr_t)b2 | (uintptr_t)cos | (uintptr_t)sin) & 7) == 0, "memlayer_rows: alignment of product 2");
     } else {

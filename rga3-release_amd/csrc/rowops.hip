@@ -495,6 +495,7 @@ extern "C" int rga3_rmsnorm_fwd(const void* x, const void* add, const void* weig
     RGA3_CHECK_ARG(x && weight && y, "rmsnorm: null pointer");
     RGA3_CHECK_ARG(rows > 0 && dim > 0 && dim % 8 == 0 && ldx % 8 == 0 && dim <= 8192, "rmsnorm: rows=%ld dim=%ld ldx=%ld", (long)rows, (long)dim, (long)ldx);
     RGA3_CHECK_ARG(!res_out || add, "rmsnorm: res_out requires add");
+    RGA3_CHECK_LD("rmsnorm", "ldx", ldx, dim, rows);
     hipStream_t st = (hipStream_t)stream;
     dim3 grid((unsigned)cdiv(rows, 4));
     const unsigned short *xp = (const unsigned short*)x, *ap = (const unsigned short*)add, *wp = (const unsigned short*)weight;
@@ -528,6 +529,8 @@ extern "C" int rga3_rmsnorm_fwd(const void* x, const void* add, const void* weig
 extern "C" int rga3_layernorm_fwd(const void* x, const void* weight, const void* bias, void* y, int64_t rows, int64_t dim,
                                   int64_t ldx, int64_t ldy, float eps, int act, void* stream) {
     RGA3_CHECK_ARG(x && weight && y, "layernorm: null pointer");
+    RGA3_CHECK_LD("layernorm", "ldx", ldx, dim, rows);
+    RGA3_CHECK_LD("layernorm", "ldy", ldy, dim, rows);
     hipStream_t st = (hipStream_t)stream;
     if (rows > 0 && dim > 0 && dim <= 16 && (dim % 8 != 0 || ldx % 8 != 0 || ldy % 8 != 0)) {
         hipLaunchKernelGGL(layernorm_tiny_kernel, dim3((unsigned)cdiv(rows, 256)), dim3(256), 0, st, (const unsigned short*)x, (const unsigned short*)weight,
@@ -554,6 +557,7 @@ extern "C" int rga3_layernorm_fwd(const void* x, const void* weight, const void*
 extern "C" int rga3_layernorm_stats(const void* x, float* stats, int64_t rows, int64_t dim, int64_t ldx, float eps, void* stream) {
     RGA3_CHECK_ARG(x && stats && rows > 0 && dim > 0 && dim % 8 == 0 && ldx % 8 == 0 && dim <= 8192, "layernorm_stats: rows=%ld dim=%ld", (long)rows, (long)dim);
     RGA3_CHECK_ARG((((uintptr_t)x) & 15) == 0 && (((uintptr_t)stats) & 7) == 0, "layernorm_stats: pointer alignment");
+    RGA3_CHECK_LD("layernorm_stats", "ldx", ldx, dim, rows);
     hipStream_t st = (hipStream_t)stream;
     const unsigned short* xp = (const unsigned short*)x;
     const unsigned short* nul = nullptr;
@@ -574,6 +578,8 @@ extern "C" int rga3_rope_inplace(void* x, const float* cos, const float* sin, in
     RGA3_CHECK_ARG(x && cos && sin, "rope: null pointer");
     RGA3_CHECK_ARG(T > 0 && nh > 0 && D > 0 && D % 16 == 0 && st % 8 == 0 && sh % 8 == 0, "rope: T=%ld nh=%d D=%d", (long)T, nh, D);
     RGA3_CHECK_ARG((((uintptr_t)cos | (uintptr_t)sin) & 15) == 0, "rope: cos/sin tables must be 16-byte aligned");
+    RGA3_CHECK_ARG(h0 >= 0, "rope: h0 %d", h0);
+    RGA3_CHECK_HEADS("rope", "x", st, sh, T, (int64_t)h0 + nh, D);
     if (nh % 4 == 0) {
         const long total = (long)T * (nh / 4) * (D / 16);
         hipLaunchKernelGGL(rope_kernel<4>, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, (unsigned short*)x, cos, sin, (long)T,
@@ -591,6 +597,8 @@ extern "C" int rga3_gather_rows(const void* table, const int64_t* idx, void* out
                                 int64_t dim, int64_t ld_table, int64_t ld_out, void* stream) {
     RGA3_CHECK_ARG(table && idx && out, "gather_rows: null pointer");
     RGA3_CHECK_ARG(n_idx > 0 && rows_per_idx > 0 && dim > 0 && dim % 8 == 0 && ld_table % 8 == 0 && ld_out % 8 == 0, "gather_rows: bad shape");
+    RGA3_CHECK_LD("gather_rows", "ld_table", ld_table, dim, 2);   // the table's row count is not passed: any index may be read
+    RGA3_CHECK_LD("gather_rows", "ld_out", ld_out, dim, n_idx * rows_per_idx);
     const long total = n_idx * rows_per_idx * (dim / 8);
     hipLaunchKernelGGL(move_rows_kernel<false>, dim3(grid1d(total)), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)table,
                        (const long*)idx, (unsigned short*)out, (long)n_idx, (long)rows_per_idx, (int)dim, (long)ld_table, (long)ld_out);
@@ -602,6 +610,8 @@ extern "C" int rga3_scatter_rows(const void* src, const int64_t* idx, void* out,
                                  int64_t ld_src, int64_t ld_out, void* stream) {
     RGA3_CHECK_ARG(src && idx && out, "scatter_rows: null pointer");
     RGA3_CHECK_ARG(n_idx > 0 && rows_per_idx > 0 && dim > 0 && dim % 8 == 0 && ld_src % 8 == 0 && ld_out % 8 == 0, "scatter_rows: bad shape");
+    RGA3_CHECK_LD("scatter_rows", "ld_src", ld_src, dim, n_idx * rows_per_idx);
+    RGA3_CHECK_LD("scatter_rows", "ld_out", ld_out, dim, 2);     // the output's row count is not passed: any index may be written
     const long total = n_idx * rows_per_idx * (dim / 8);
     hipLaunchKernelGGL(move_rows_kernel<true>, dim3(grid1d(total)), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)src,
                        (const long*)idx, (unsigned short*)out, (long)n_idx, (long)rows_per_idx, (int)dim, (long)ld_src, (long)ld_out);
@@ -611,7 +621,9 @@ extern "C" int rga3_scatter_rows(const void* src, const int64_t* idx, void* out,
 
 extern "C" int rga3_pad_cols(const void* src, void* dst, int64_t rows, int64_t cols, int64_t ld_src, int64_t ld_dst, void* stream) {
     RGA3_CHECK_ARG(src && dst, "pad_cols: null pointer");
-    RGA3_CHECK_ARG(rows > 0 && cols > 0 && ld_dst >= cols && ld_dst % 8 == 0, "pad_cols: bad shape");
+    RGA3_CHECK_ARG(rows > 0 && cols > 0 && ld_dst % 8 == 0, "pad_cols: bad shape (ld_dst a multiple of 8)");
+    RGA3_CHECK_LD("pad_cols", "ld_dst", ld_dst, cols, 2);
+    RGA3_CHECK_LD("pad_cols", "ld_src", ld_src, cols, rows);
     hipLaunchKernelGGL(pad_cols_kernel, dim3(grid1d(rows * (ld_dst / 8))), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)src,
                        (unsigned short*)dst, (long)rows, (int)cols, (long)ld_src, (long)ld_dst);
     RGA3_CHECK_LAUNCH("pad_cols");
@@ -637,7 +649,8 @@ extern "C" int rga3_add(const void* a, const void* b, void* out, int64_t n, void
 extern "C" int rga3_cross_entropy_rows(const void* logits, int logits_dtype, const int64_t* labels, float* row_loss,
                                        void* dlogits, int64_t rows, int64_t V, int64_t ld, float grad_scale, void* stream) {
     RGA3_CHECK_ARG(logits && labels && row_loss, "cross_entropy: null pointer");
-    RGA3_CHECK_ARG(rows > 0 && V > 0 && ld >= V, "cross_entropy: bad shape");
+    RGA3_CHECK_ARG(rows > 0 && V > 0, "cross_entropy: bad shape");
+    RGA3_CHECK_LD("cross_entropy", "ld", ld, V, 2);
     RGA3_CHECK_ARG(logits_dtype == RGA3_BF16 || logits_dtype == RGA3_F32, "cross_entropy: dtype");
     hipStream_t st = (hipStream_t)stream;
     if (logits_dtype == RGA3_F32)

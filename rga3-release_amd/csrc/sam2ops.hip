@@ -478,7 +478,8 @@ extern "C" int rga3_im2col(const void* img, void* out, int64_t F, int C, int H, 
                            void* stream) {
     RGA3_CHECK_ARG(img && out && F > 0 && C > 0 && H > 0 && W > 0 && ks > 0 && stride > 0, "im2col: bad args");
     const int Ho = (H + 2 * pad - ks) / stride + 1, Wo = (W + 2 * pad - ks) / stride + 1;
-    RGA3_CHECK_ARG(ld_out >= (int64_t)C * ks * ks && ld_out % 8 == 0 && (((uintptr_t)out) & 15) == 0, "im2col: ld_out too small / not a multiple of 8, or out not 16-byte aligned");
+    RGA3_CHECK_ARG(ld_out % 8 == 0 && (((uintptr_t)out) & 15) == 0, "im2col: ld_out not a multiple of 8, or out not 16-byte aligned");
+    RGA3_CHECK_LD("im2col", "ld_out", ld_out, (int64_t)C * ks * ks, 2);
     hipLaunchKernelGGL(im2col_kernel, dim3(grid1d(F * Ho * Wo * (ld_out / 8))), dim3(256), 0, (hipStream_t)stream, (cus)img, (us)out, (int)F, C, H, W, ks,
                        stride, pad, Ho, Wo, (int)ld_out);
     RGA3_CHECK_LAUNCH("im2col");
@@ -487,6 +488,8 @@ extern "C" int rga3_im2col(const void* img, void* out, int64_t F, int C, int H, 
 
 extern "C" int rga3_maxpool2x2_win(const void* x, void* y, int64_t nwin, int w, int C, int64_t ldx, int64_t ldy, void* stream) {
     RGA3_CHECK_ARG(x && y && nwin > 0 && w >= 2 && w % 2 == 0 && C % 8 == 0 && ldx % 8 == 0 && ldy % 8 == 0, "maxpool2x2_win: bad args");
+    RGA3_CHECK_LD("maxpool2x2_win", "ldx", ldx, C, nwin * w * w);
+    RGA3_CHECK_LD("maxpool2x2_win", "ldy", ldy, C, nwin * (w / 2) * (w / 2));
     hipLaunchKernelGGL(maxpool_win_kernel, dim3(grid1d(nwin * (w / 2) * (w / 2) * (C / 8))), dim3(256), 0, (hipStream_t)stream, (cus)x, (us)y,
                        (long)nwin, w, C, (long)ldx, (long)ldy);
     RGA3_CHECK_LAUNCH("maxpool2x2_win");
@@ -503,6 +506,9 @@ extern "C" int rga3_upsample2x_add(const void* a, const void* b, void* out, int6
 extern "C" int rga3_add_bcast(const void* a, const void* b, void* out, int64_t rows, int64_t rows_b, int C, int64_t lda, int64_t ldb,
                               int64_t ldo, float alpha, void* stream) {
     RGA3_CHECK_ARG(a && b && out && rows > 0 && rows_b > 0 && C % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0 && ldo % 8 == 0, "add_bcast: bad args");
+    RGA3_CHECK_LD("add_bcast", "lda", lda, C, rows);
+    RGA3_CHECK_LD("add_bcast", "ldb", ldb, C, rows_b < rows ? rows_b : rows);
+    RGA3_CHECK_LD("add_bcast", "ldo", ldo, C, rows);
     hipLaunchKernelGGL(add_bcast_kernel, dim3(grid1d(rows * (C / 8))), dim3(256), 0, (hipStream_t)stream, (cus)a, (cus)b, (us)out, (long)rows,
                        (long)rows_b, C, (long)lda, (long)ldb, (long)ldo, alpha);
     RGA3_CHECK_LAUNCH("add_bcast");
@@ -592,6 +598,7 @@ extern "C" int rga3_dwconv7x7(const void* x, const void* w, const void* bias, vo
 
 extern "C" int rga3_rope_axial_inplace(void* x, const float* cos, const float* sin, int64_t n_rope, int nq, int C, int64_t ldx, void* stream) {
     RGA3_CHECK_ARG(x && cos && sin && nq > 0 && C % 8 == 0 && ldx % 8 == 0, "rope_axial: bad args");
+    RGA3_CHECK_LD("rope_axial", "ldx", ldx, C, n_rope);
     if (n_rope <= 0) return 0;
     hipLaunchKernelGGL(rope_axial_kernel, dim3(grid1d(n_rope * (C / 8))), dim3(256), 0, (hipStream_t)stream, (us)x, cos, sin, (long)n_rope, nq, C, (long)ldx);
     RGA3_CHECK_LAUNCH("rope_axial");

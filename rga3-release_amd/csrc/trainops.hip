@@ -454,7 +454,9 @@ extern "C" int rga3_swiglu_fwd(const void* gu, void* a, int64_t T, int64_t I, vo
 }
 
 extern "C" int rga3_transpose16(const void* in, void* out, int64_t R, int64_t C, int64_t ld_in, int64_t ld_out, void* stream) {
-    RGA3_CHECK_ARG(in && out && R > 0 && C > 0 && ld_in >= C && ld_out >= R, "transpose16: bad args");
+    RGA3_CHECK_ARG(in && out && R > 0 && C > 0, "transpose16: bad args");
+    RGA3_CHECK_LD("transpose16", "ld_in", ld_in, C, 2);
+    RGA3_CHECK_LD("transpose16", "ld_out", ld_out, R, 2);
     RGA3_CHECK_ARG(cdiv(R, 64) <= 65535, "transpose16: too many rows");
     hipLaunchKernelGGL(transpose16_kernel, dim3((unsigned)cdiv(C, 64), (unsigned)cdiv(R, 64)), dim3(256), 0, (hipStream_t)stream, (cus)in, (us)out, (long)R,
                        (long)C, (long)ld_in, (long)ld_out);
@@ -485,6 +487,7 @@ extern "C" int rga3_transpose16_many(const void* const* ptrs, const int64_t* dim
 extern "C" int rga3_segment_sum_rows(const void* x, const int64_t* rows, const int64_t* offsets, void* out, int64_t n_out, int64_t dim,
                                      int64_t ldx, void* stream) {
     RGA3_CHECK_ARG(x && rows && offsets && out && n_out > 0 && dim % 8 == 0 && ldx % 8 == 0, "segment_sum_rows: bad args");
+    RGA3_CHECK_LD("segment_sum_rows", "ldx", ldx, dim, 2);   // the row count of x is not passed: any index may be read
     hipLaunchKernelGGL(segment_sum_rows_kernel, dim3((unsigned)n_out), dim3(256), 0, (hipStream_t)stream, (cus)x, (const long*)rows, (const long*)offsets,
                        (us)out, (int)dim, (long)ldx);
     RGA3_CHECK_LAUNCH("segment_sum_rows");
@@ -551,6 +554,8 @@ extern "C" int rga3_adamw_step_clip_rows(void* param, float* master, const void*
 extern "C" int rga3_scatter_add_rows(void* dst, const int64_t* idx, const void* src, int64_t n, int64_t dim, int64_t ld_dst, int64_t ld_src, float scale,
                                      void* stream) {
     RGA3_CHECK_ARG(dst && idx && src && n > 0 && dim > 0 && dim % 8 == 0 && ld_dst % 8 == 0 && ld_src % 8 == 0, "scatter_add_rows: bad args");
+    RGA3_CHECK_LD("scatter_add_rows", "ld_dst", ld_dst, dim, 2);   // the row count of dst is not passed: any index may be written
+    RGA3_CHECK_LD("scatter_add_rows", "ld_src", ld_src, dim, n);
     hipLaunchKernelGGL(scatter_add_rows_kernel, dim3(grid1d(n * (dim / 8))), dim3(256), 0, (hipStream_t)stream, (us)dst, (const long*)idx, (cus)src, (long)n, (int)dim,
                        (long)ld_dst, (long)ld_src, scale);
     RGA3_CHECK_LAUNCH("scatter_add_rows");
