@@ -105,7 +105,7 @@ int64_t rga3_gemm_workspace_bytes(void);
 /* C[M,N] (bf16 / f32) = A^T . B (+ bias[n]); A [K,M], B [K,N] bf16 row-major (K = tokens): the weight-gradient product dW = dY^T X of
  * nn.Linear / LoRA (autograd under reference train_joint.py:534) without transposing the activations first.  M, N multiples of 8.
  * workspace (optional, caller-owned, 16-byte aligned): with few output tiles over many tokens (LoRA dW: 128 x 3584 over 2112-4160 tokens) K is
- * cut into <= 64 slices whose f32 partial sums (Z * M * N * 4 bytes) are added in fixed slice order -- by a second launch, or, with `counters` (>= 128 32-bit
+ * cut into <= 64 slices whose f32 partial sums (Z * M * N * 4 bytes; Z = rga3_gemm_tn_slices(M, N, K) uses every slice) are added in fixed slice order -- by a second launch, or, with `counters` (>= 128 32-bit
  * words, zeroed ONCE by the caller and kept for the calls of one stream: the kernel leaves them zero), inside the same launch by the workgroup that reaches an output
  * tile last (which one is timing, the order of the additions is not: deterministic). */
 int rga3_gemm_tn_bf16(const void* A, const void* B, const void* bias, void* C, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb,
@@ -113,7 +113,7 @@ int rga3_gemm_tn_bf16(const void* A, const void* B, const void* bias, void* C, i
 /* n (<= 4) such products in ONE launch (+ one slab-sum launch): the four LoRA weight gradients of a decoder layer (dB_q, dA_q, dB_v, dA_v: autograd of PEFT's
  * lora_A / lora_B under reference train_joint.py:193-232, 534) were four launches of 1 - 28 tiles and four slab sums.  ptrs: n x 3 {A, B, C}; dims: n x 7
  * {M, N, K, lda, ldb, ldc, out_dtype}; HOST arrays.  Every product is K-split exactly as rga3_gemm_tn_bf16 with a full-size workspace splits it (same bits); the
- * caller's workspace must hold sum_i Z_i M_i N_i floats, Z_i = min(64, 256 / tiles_i, K_i / 256) (>= 1), or the call fails. */
+ * caller's workspace must hold sum_i Z_i M_i N_i floats, Z_i = rga3_gemm_tn_slices(M_i, N_i, K_i), or the call fails. */
 int rga3_gemm_tn_many(const void* const* ptrs, const int64_t* dims, int n, void* workspace, int64_t workspace_bytes, void* stream);
 
 
@@ -382,6 +382,16 @@ int rga3_gemm_ragged_plan(int64_t M, int64_t N, int64_t K, int cus, int split, i
  * ids / bm / bn (tile id, tile rows, tile columns) and returns the number of tilings (so cap = 0 asks for the count); < 0 on an unknown entry.  The entry points
  * validate their `tile` argument against the same table. */
 int rga3_gemm_tiles(int entry, int* ids, int* bm, int* bn, int cap);
+/* Host only: the tilings a tuner should time for ONE product, in trial order (a tuner that keeps the first of equal times depends on the order).  entry as in
+ * rga3_gemm_tiles (rga3_gemm_swiglu_pre_bf16: entry 0 with RGA3_ACT_SWIGLU; entry 5: N = the width of the first pair); act / out_dtype as the entry point takes them;
+ * epilogue: bit 0 bias, bit 1 residual, bit 2 column scale.  The tilings made for one kind of shape (split-K 25, the skinny 14, token rows 41, the 192-wide 23) are
+ * listed only where they apply; with an N side only widths that divide N.  Fills the first `cap` entries of ids and returns the number of tilings (cap = 0 asks for
+ * the count); < 0 = bad arguments.  No reference counterpart (the reference's GEMMs are vendor BLAS calls). */
+int rga3_gemm_candidates(int entry, int64_t M, int64_t N, int64_t K, int act, int out_dtype, int epilogue, int* ids, int cap);
+/* Host only: the number of K slices rga3_gemm_tn_bf16 (given room for all of them) and rga3_gemm_tn_many cut C [M, N] = A^T B over K rows into = the M x N f32 slabs
+ * the caller's workspace must hold; 1 = no split.  The entry points may launch fewer slices (whole K-tile runs), never more.  < 0 = bad arguments.  No reference
+ * counterpart. */
+int rga3_gemm_tn_slices(int64_t M, int64_t N, int64_t K);
 /* (the 32-bit word BEHIND that counter is a fault-injection switch for tests: 0 in every real run -- the caller zeroes the flag page; 0xffffffff makes every stream-K
  * owner behave as if its contributors never publish; any other value is the spin limit) */
 /* dx = d rmsnorm(x; weight)/dx . dy (+ add): backward of HF Qwen2_5_VLRMSNorm (modeling_qwen2_5_vl.py:74-79) w.r.t. x */

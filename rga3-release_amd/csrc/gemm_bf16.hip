@@ -2642,7 +2642,8 @@ static int pick_tile(int M, int N, int K, bool plain, int forced) {
 }
 
 // ---- The tilings.  One row per tile id: which kernel family runs it, its shape, and which entry points have a kernel for it.  Every validity check, the dispatch
-// (launch_tile), rga3_gemm_lnsum_slices and rga3_gemm_tiles (from which rga3.hip.ops takes its candidate lists) read this table: a new tiling is a new row.
+// (launch_tile), rga3_gemm_lnsum_slices, rga3_gemm_tiles and rga3_gemm_candidates (the tilings rga3.hip.tuner times for a product: the order lists and tuned_for below)
+// read this table: a new tiling is a new row, plus its id in the order list of every entry point that is to tune it.
 // Families: F_SINGLE gemm_nt_kernel (one tile per workgroup, one barrier phase per K-tile); F_PP gemm_nt_pp_kernel (ping-pong on eight waves, one tile per workgroup);
 // F_SK gemm_nt_sk_kernel (persistent: one workgroup per CU; Tile::sk adds the stream-K tail / the ragged-row loop); F_SPLITK split-K for few tiles over a very long K
 // (falls back to F_SK / F_PP where it does not apply); F_SPLIT64 64 x 64 with a K split (plain products; anything else runs as the single-phase 64 x 64); F_W4 256 x 256
@@ -2692,6 +2693,11 @@ constexpr int kNumTiles = (int)(sizeof(kTiles) / sizeof(kTiles[0]));
 
 // rga3_gemm_tiles lists an entry point's tilings in the order the tuner is to try them (rga3.hip.tuner.pick times the candidates in the order given): that order is
 // behaviour, and no single row order serves all four.  E_PLAIN / E_SHARED come in row order.
+// kOrderTuned is what the tuner times for those two (rga3_gemm_candidates): 256 x 256 ping-pong: one tile per workgroup / persistent / persistent + stream-K tail /
+// persistent with the ragged-row loop; 256 x 256 on four waves; 192 x 256 persistent / + stream-K tail (M = 2112 = 11 x 192); single-phase 128 x 128, 64 x 64, 128 x 256,
+// 128 x 320, 128 x 192; 128 x 256 with three LDS stages.  kExtraPlain follows it for rga3_gemm_bf16, each id under its predicate in tuned_for.
+constexpr int kOrderTuned[] = {20, 21, 22, 27, 28, 31, 32, 12, 13, 3, 4, 5, 6};
+constexpr int kExtraPlain[] = {25, 14, 41, 23};
 constexpr int kOrderLn[] = {20, 3, 5, 12, 13, 6, 7};
 constexpr int kOrderLnsum[] = {20, 3, 5, 12, 13, 23};
 constexpr int kOrderCatK[] = {12, 3, 4, 5, 6, 13};
@@ -2710,6 +2716,36 @@ constexpr bool order_matches_table(int entry) {   // an order list names, once e
     return rows == kOrders[entry].n;
 }
 static_assert(order_matches_table(2) && order_matches_table(3) && order_matches_table(4) && order_matches_table(5), "kOrder* and kTiles disagree");
+
+constexpr bool tuned_run_everywhere() {   // one list serves rga3_gemm_bf16, rga3_gemm_rms_bf16 and rga3_gemm_swiglu_pre_bf16: every id has a kernel with the shared epilogue
+    for (int id : kOrderTuned) {
+        bool ok = false;
+        for (const Tile& t : kTiles) ok |= t.id == id && (t.entries & PS) == PS;
+        if (!ok) return false;
+    }
+    return true;
+}
+static_assert(tuned_run_everywhere(), "kOrderTuned names a tiling without E_PLAIN | E_SHARED");
+
+// What rga3_gemm_candidates asks about: a product as its entry point sees it.
+struct Product {
+    int64_t M, N, K;
+    int act, out_dtype;
+    bool bias, residual, colscale;
+};
+// Token rows (tile 41): the shapes its kernel takes, which rga3_gemm_bf16 checks and the tuner asks about.
+static bool rows16_ok(int64_t M, bool colscale, int out_dtype, int act) { return M <= 16 && !colscale && out_dtype == RGA3_BF16 && act != ACT_SWIGLU; }
+// Whether the tuner is to time tiling t of entry point `entry` (rga3_gemm_tiles' numbering) for product p: the tilings made for one kind of shape are timed there only.
+static bool tuned_for(const Tile& t, int entry, const Product& p) {
+    const bool plain = p.act == ACT_NONE && !p.residual && !p.colscale;
+    switch (t.id) {
+        case 25: return plain && p.M * p.N <= (1 << 20) && p.K >= 4096;   // few output tiles over a very long K (weight gradients dW = dY^T X): the split-K form
+        case 14: return plain && !p.bias && p.N % 8 == 0 && p.M * p.N <= (1 << 19) && p.K >= 512;   // skinny products (LoRA x A^T, dY B): 64 x 64 tiles with a K split
+        case 41: return rows16_ok(p.M, p.colscale, p.out_dtype, p.act);   // (products below the tuner's work threshold take it without asking: gemm_bf16_impl)
+        case 23: return p.act == ACT_NONE && p.N % 192 == 0 && p.N % 256 != 0 && p.M >= 1024;   // widths of 3 / 9 x 192 (Hiera stage 3): the ping-pong loop on 256 x 192 tiles
+        default: return entry != 5 || p.N % t.bn == 0;   // with an N side the first pair's width is whole tile columns
+    }
+}
 
 // The row of tile `id` when the entry point has a kernel for it, else null.  -1 is tile 12 (rga3_gemm_bf16 alone replaces it by pick_tile's choice).
 static const Tile* find_tile(int id, unsigned entry) {
@@ -2784,6 +2820,28 @@ static int tn_slices(int64_t M, int64_t N, int64_t K, int64_t ws_bytes) {
     if (Z > nk / 8) Z = nk / 8;
     if (Z > fit) Z = fit;
     return Z < 2 ? 1 : (int)Z;
+}
+
+// What both TN entry points check and fill for one product (`who` prefixes the messages: the entry point, and in the grouped form the product); no K split yet.
+static int tn_args(GemmArgs& a, TnArgs& t, const char* who, const void* A, const void* B, void* C, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb,
+                   int64_t ldc, int out_dtype) {
+    RGA3_CHECK_ARG(A && B && C, "%s: null pointer", who);
+    RGA3_CHECK_ARG(M >= 8 && N >= 8 && K > 0 && M % 8 == 0 && N % 8 == 0, "%s: bad shape M=%ld N=%ld K=%ld (M, N multiples of 8)", who, (long)M, (long)N, (long)K);
+    RGA3_CHECK_ARG(lda % 8 == 0 && ldb % 8 == 0 && ldc % 4 == 0, "%s: lda/ldb must be multiples of 8 elements, ldc of 4", who);
+    RGA3_CHECK_ARG((((uintptr_t)A | (uintptr_t)B | (uintptr_t)C) & 15) == 0, "%s: pointers must be 16-byte aligned", who);
+    RGA3_CHECK_ARG(out_dtype == RGA3_BF16 || out_dtype == RGA3_F32, "%s: out_dtype %d", who, out_dtype);
+    RGA3_CHECK_LD(who, "lda", lda, M, K);
+    RGA3_CHECK_LD(who, "ldb", ldb, N, K);
+    RGA3_CHECK_LD(who, "ldc", ldc, N, M);
+    a = GemmArgs{};
+    a.C = C;
+    a.M = (int)M; a.N = (int)N; a.K = (int)K;
+    a.ldc = ldc;
+    a.ntm = (int)cdiv(M, 128); a.ntn = (int)cdiv(N, 128); a.group_m = 1;
+    t = TnArgs{};
+    t.A = (const unsigned short*)A; t.B = (const unsigned short*)B; t.lda = lda; t.ldb = ldb; t.K = (int)K;
+    t.kt_per_z = (int)cdiv(K, 32);   // all K-tiles
+    return 0;
 }
 
 }  // namespace rga3
@@ -2878,6 +2936,34 @@ extern "C" int rga3_gemm_tiles(int entry, int* ids, int* bm, int* bn, int cap) {
     return n;
 }
 
+// Host only (no device needed): the tilings the tuner is to time for one product, in trial order (rga3.hip.tuner keeps the first of equal times, so the order is
+// behaviour).  entry as in rga3_gemm_tiles (rga3_gemm_swiglu_pre_bf16: entry 0 with RGA3_ACT_SWIGLU; entry 5: N = the width of the first pair); epilogue: bit 0 bias,
+// bit 1 residual, bit 2 column scale.  Fills the first `cap` of ids and returns the number of tilings; < 0 on bad arguments.
+extern "C" int rga3_gemm_candidates(int entry, int64_t M, int64_t N, int64_t K, int act, int out_dtype, int epilogue, int* ids, int cap) {
+    RGA3_CHECK_ARG(entry >= 0 && entry < kNumEntries && cap >= 0 && (cap == 0 || ids), "gemm_candidates: entry %d (0..%d), cap %d", entry, kNumEntries - 1, cap);
+    RGA3_CHECK_ARG(M > 0 && N > 0 && K > 0, "gemm_candidates: bad shape M=%ld N=%ld K=%ld", (long)M, (long)N, (long)K);
+    RGA3_CHECK_ARG(act >= 0 && act <= 3 && (out_dtype == RGA3_BF16 || out_dtype == RGA3_F32) && epilogue >= 0 && epilogue < 8,
+                   "gemm_candidates: act %d, out_dtype %d, epilogue %d", act, out_dtype, epilogue);
+    const Product p{M, N, K, act, out_dtype, (epilogue & 1) != 0, (epilogue & 2) != 0, (epilogue & 4) != 0};
+    const TileOrder lists[2] = {entry < 2 ? TileOrder{kOrderTuned, (int)(sizeof(kOrderTuned) / sizeof(int))} : kOrders[entry],
+                                entry == 0 ? TileOrder{kExtraPlain, (int)(sizeof(kExtraPlain) / sizeof(int))} : TileOrder{nullptr, 0}};
+    int n = 0;
+    for (const TileOrder& o : lists)
+        for (int i = 0; i < o.n; ++i)
+            if (tuned_for(*find_tile(o.ids[i], 1u << entry), entry, p)) {
+                if (n < cap) ids[n] = o.ids[i];
+                ++n;
+            }
+    return n;
+}
+
+// Host only (no device needed): the K slices rga3_gemm_tn_bf16 / rga3_gemm_tn_many cut a product into when the workspace has room for all of them = the number of
+// M x N f32 slabs a caller's workspace must hold (1: no split); the entry points then round it to whole K-tile runs, never up.  < 0 on bad arguments.
+extern "C" int rga3_gemm_tn_slices(int64_t M, int64_t N, int64_t K) {
+    RGA3_CHECK_ARG(M > 0 && N > 0 && K > 0, "gemm_tn_slices: bad shape M=%ld N=%ld K=%ld", (long)M, (long)N, (long)K);
+    return tn_slices(M, N, K, INT64_MAX);
+}
+
 static int gemm_bf16_impl(const void* A, const void* W, const void* bias, const void* residual, const void* colscale, void* C,
                           int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldw, int64_t ldc, int64_t ldr,
                           int act, int out_dtype, int tile, void* workspace, int64_t workspace_bytes, const unsigned long long* rs_in, int64_t rs_width, float rs_eps,
@@ -2899,9 +2985,9 @@ static int gemm_bf16_impl(const void* A, const void* W, const void* bias, const 
     a.pre = (unsigned short*)pre; a.ldpre = ldpre;
     hipStream_t st = (hipStream_t)stream;
     RGA3_CHECK_ARG(tile != 40 || (M <= 4 && !colscale), "gemm: the skinny kernel (tile 40) takes M <= 4 rows and no column scale");
-    const bool rows16_ok = M <= 16 && !colscale && out_dtype == RGA3_BF16 && act != ACT_SWIGLU;
-    RGA3_CHECK_ARG(tile != 41 || rows16_ok, "gemm: the token-row kernel (tile 41) takes M <= 16 rows, bf16 output, no column scale, no SwiGLU");
-    int tl = (tile == -1 && M <= 4 && !colscale) ? 40 : (tile == -1 && rows16_ok) ? 41 : pick_tile((int)M, (int)N, (int)K, act == ACT_NONE && !residual && !colscale && !rs_in && !rs_out, tile);   // row sums live in the shared epilogue: never the split-K tile
+    const bool rows16 = rows16_ok(M, colscale != nullptr, out_dtype, act);
+    RGA3_CHECK_ARG(tile != 41 || rows16, "gemm: the token-row kernel (tile 41) takes M <= 16 rows, bf16 output, no column scale, no SwiGLU");
+    int tl = (tile == -1 && M <= 4 && !colscale) ? 40 : (tile == -1 && rows16) ? 41 : pick_tile((int)M, (int)N, (int)K, act == ACT_NONE && !residual && !colscale && !rs_in && !rs_out, tile);   // row sums live in the shared epilogue: never the split-K tile
     if (out_dtype == RGA3_F32) return launch_tile<ACT_NONE, true, 0>(a, tl, st);
     switch (act) {
         case ACT_NONE: return launch_tile<ACT_NONE, false, 0>(a, tl, st);
@@ -3036,31 +3122,17 @@ extern "C" int rga3_gemm_lnq_bf16(const void* A, const void* Wf, const void* bia
 // transposing either operand first.  M, N multiples of 8; lda / ldb / ldc in elements.
 extern "C" int rga3_gemm_tn_bf16(const void* A, const void* B, const void* bias, void* C, int64_t M, int64_t N, int64_t K, int64_t lda,
                                  int64_t ldb, int64_t ldc, int out_dtype, void* workspace, int64_t workspace_bytes, void* counters, void* stream) {
-    RGA3_CHECK_ARG(A && B && C, "gemm_tn: null pointer");
-    RGA3_CHECK_ARG(M >= 8 && N >= 8 && K > 0 && M % 8 == 0 && N % 8 == 0, "gemm_tn: bad shape M=%ld N=%ld K=%ld (M, N multiples of 8)", (long)M, (long)N, (long)K);
-    RGA3_CHECK_ARG(lda % 8 == 0 && ldb % 8 == 0 && ldc % 4 == 0, "gemm_tn: lda/ldb must be multiples of 8 elements, ldc of 4");
-    RGA3_CHECK_ARG((((uintptr_t)A | (uintptr_t)B | (uintptr_t)C | (uintptr_t)workspace) & 15) == 0, "gemm_tn: pointers must be 16-byte aligned");
-    RGA3_CHECK_ARG(out_dtype == RGA3_BF16 || out_dtype == RGA3_F32, "gemm_tn: out_dtype %d", out_dtype);
-    RGA3_CHECK_ARG(cdiv(M, 128) <= 65535, "gemm_tn: M too large");
-    RGA3_CHECK_LD("gemm_tn", "lda", lda, M, K);
-    RGA3_CHECK_LD("gemm_tn", "ldb", ldb, N, K);
-    RGA3_CHECK_LD("gemm_tn", "ldc", ldc, N, M);
     GemmArgs a;
-    a.A = nullptr; a.W = nullptr; a.C = C;
-    a.bias = (const unsigned short*)bias; a.res = nullptr; a.colscale = nullptr;
-    a.M = (int)M; a.N = (int)N; a.K = (int)K;
-    a.lda = 0; a.ldw = 0; a.ldc = ldc; a.ldr = 0;
-    a.ntm = (int)cdiv(M, 128); a.ntn = (int)cdiv(N, 128); a.group_m = 1;
-    a.ws = nullptr; a.ws_bytes = 0; a.ksl = 0; a.rowstat = nullptr; a.colc = nullptr;
     TnArgs t;
-    t.A = (const unsigned short*)A; t.B = (const unsigned short*)B; t.lda = lda; t.ldb = ldb; t.K = (int)K;
-    t.counters = nullptr; t.out = nullptr; t.ldo = 0; t.out_f32 = 0;
-    const int nk = (int)cdiv(K, 32);
+    if (int rc = tn_args(a, t, "gemm_tn", A, B, C, M, N, K, lda, ldb, ldc, out_dtype)) return rc;
+    RGA3_CHECK_ARG((((uintptr_t)workspace) & 15) == 0, "gemm_tn: pointers must be 16-byte aligned");
+    RGA3_CHECK_ARG(cdiv(M, 128) <= 65535, "gemm_tn: M too large");
+    a.bias = (const unsigned short*)bias;
+    const int nk = t.kt_per_z;
     const long tiles = (long)a.ntm * a.ntn;
     int Z = (workspace && !bias) ? tn_slices(M, N, K, workspace_bytes) : 1;   // the slabs live in the caller's workspace; the slab sum adds no bias
     hipStream_t st = (hipStream_t)stream;
     if (Z == 1) {
-        t.kt_per_z = nk; t.slab = 0;
         dim3 grid((unsigned)a.ntn, (unsigned)a.ntm);
         if (out_dtype == RGA3_F32) hipLaunchKernelGGL(gemm_tn_kernel<true>, grid, dim3(256), 0, st, a, t);
         else hipLaunchKernelGGL(gemm_tn_kernel<false>, grid, dim3(256), 0, st, a, t);
@@ -3102,25 +3174,12 @@ extern "C" int rga3_gemm_tn_many(const void* const* ptrs, const int64_t* dims, i
         void* C = (void*)ptrs[3 * i + 2];
         const int64_t M = dims[7 * i], N = dims[7 * i + 1], K = dims[7 * i + 2], lda = dims[7 * i + 3], ldb = dims[7 * i + 4], ldc = dims[7 * i + 5];
         const int out_dtype = (int)dims[7 * i + 6];
-        RGA3_CHECK_ARG(A && B && C, "gemm_tn_many: null pointer (product %d)", i);
-        RGA3_CHECK_ARG(M >= 8 && N >= 8 && K > 0 && M % 8 == 0 && N % 8 == 0, "gemm_tn_many: bad shape M=%ld N=%ld K=%ld (product %d)", (long)M, (long)N, (long)K, i);
-        RGA3_CHECK_ARG(lda % 8 == 0 && ldb % 8 == 0 && ldc % 4 == 0, "gemm_tn_many: lda/ldb must be multiples of 8 elements, ldc of 4 (product %d)", i);
-        RGA3_CHECK_ARG((((uintptr_t)A | (uintptr_t)B | (uintptr_t)C) & 15) == 0, "gemm_tn_many: pointers must be 16-byte aligned (product %d)", i);
-        RGA3_CHECK_ARG(out_dtype == RGA3_BF16 || out_dtype == RGA3_F32, "gemm_tn_many: out_dtype %d", out_dtype);
-        RGA3_CHECK_LD("gemm_tn_many", "lda", lda, M, K);
-        RGA3_CHECK_LD("gemm_tn_many", "ldb", ldb, N, K);
-        RGA3_CHECK_LD("gemm_tn_many", "ldc", ldc, N, M);
+        char who[40];
+        snprintf(who, sizeof(who), "gemm_tn_many (product %d)", i);
         GemmArgs& a = P.a[i];
-        a = GemmArgs();
-        a.A = nullptr; a.W = nullptr; a.bias = nullptr; a.res = nullptr; a.colscale = nullptr;
-        a.M = (int)M; a.N = (int)N; a.K = (int)K;
-        a.lda = 0; a.ldw = 0; a.ldr = 0;
-        a.ntm = (int)cdiv(M, 128); a.ntn = (int)cdiv(N, 128); a.group_m = 1;
-        a.ws = nullptr; a.ws_bytes = 0; a.ksl = 0; a.rowstat = nullptr; a.colc = nullptr;
         TnArgs& t = P.t[i];
-        t.A = (const unsigned short*)A; t.B = (const unsigned short*)B; t.lda = lda; t.ldb = ldb; t.K = (int)K;
-        t.counters = nullptr; t.out = nullptr; t.ldo = 0; t.out_f32 = 0;
-        const int nk = (int)cdiv(K, 32);
+        if (int rc = tn_args(a, t, who, A, B, C, M, N, K, lda, ldb, ldc, out_dtype)) return rc;
+        const int nk = t.kt_per_z;
         const long tiles = (long)a.ntm * a.ntn;
         int Z = tn_slices(M, N, K, INT64_MAX);   // the slices of the single form with room for all of them: a short workspace is an error below
         t.kt_per_z = (int)cdiv(nk, Z);

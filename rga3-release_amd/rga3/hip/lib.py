@@ -80,6 +80,8 @@ SIGNATURES = {
     "rga3_gemm_timeout_counter_offset": [],
     "rga3_gemm_ragged_plan": [_i64, _i64, _i64, _i, _i, _p, _p],
     "rga3_gemm_tiles": [_i, _p, _p, _p, _i],
+    "rga3_gemm_candidates": [_i, _i64, _i64, _i64, _i, _i, _i, _p, _i],
+    "rga3_gemm_tn_slices": [_i64, _i64, _i64],
     "rga3_quant_fp8_rows": [_p, _p, _p, _i64, _i64, _i64, _i64, _p],
     "rga3_gemm_fp8": [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _p],
     "rga3_swiglu_fwd_quant_fp8": [_p, _p, _p, _i64, _i64, _p],
@@ -172,6 +174,23 @@ def gemm_tiles(entry: str) -> dict:
             raise Rga3Error("rga3_gemm_tiles failed: " + last_error())
         _tiles[entry] = {ids[i]: bn[i] for i in range(n)}
     return _tiles[entry]
+
+
+def gemm_candidates(entry: str, M: int, N: int, K: int, act: int = 0, out_dtype: int = 0, bias=False, residual=False, colscale=False) -> tuple:
+    """The tilings the tuner is to time for one product of a bf16 GEMM entry point, in trial order (rga3_gemm_candidates: host only, no device call)."""
+    ids = (C.c_int * 64)()
+    n = load().rga3_gemm_candidates(_TILE_ENTRIES.index(entry), M, N, K, act, out_dtype, bool(bias) | bool(residual) << 1 | bool(colscale) << 2, ids, 64)
+    if not 0 <= n <= 64:
+        raise Rga3Error("rga3_gemm_candidates failed: " + last_error())
+    return tuple(ids[:n])
+
+
+def gemm_tn_slices(M: int, N: int, K: int) -> int:
+    """The M x N f32 slabs the workspace of a TN product needs (rga3_gemm_tn_slices: host only); 1 = the product is not split over K."""
+    n = load().rga3_gemm_tn_slices(M, N, K)
+    if n < 1:
+        raise Rga3Error("rga3_gemm_tn_slices failed: " + last_error())
+    return n
 
 
 def check(rc: int, what: str):

@@ -92,6 +92,16 @@ def gemm_stream_k_timeouts(device=None) -> int:
     return tot
 
 
+_TUNE_WORK = 1 << 24    # M * N * K below which gemm / gemm_swiglu_pre / gemm_lnsum / gemm_ln do not tune: the library's own choice (tile = -1) runs the product
+
+
+def _tuned(key, run, entry: str, candidates):
+    """The tuner's tiling for `key` if the entry point `entry` (as rga3.hip.lib.gemm_tiles names it) has a kernel for it, else -1: a tiling forced for the plain
+    GEMMs (tuner.force), or decided for another entry point's product under the same key, may be one with an epilogue of its own."""
+    tile = _tuner.pick(key, run, candidates)
+    return tile if tile in _lib.gemm_tiles(entry) else -1
+
+
 def gemm(a: torch.Tensor, w: torch.Tensor, bias=None, residual=None, act: str = "none", out_dtype=torch.bfloat16,
          out=None, tile: int = -1, colscale=None, rms_in=None, rms_out=None) -> torch.Tensor:
     """out = residual + colscale * act(a @ w.T + bias).  a [M,K], w [N,K] (nn.Linear layout), bf16.
@@ -148,25 +158,16 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias=None, residual=None, act: str = 
                           out.stride(0), ldr, ACT[act], odt, t, ws.data_ptr(), ws.numel(), _stream()), "gemm_bf16")
 
     if rms:
-        if tile == -1:
-            tile = _tuner.pick(_tuner.key_of(M, N, K, act, odt, bias is not None, residual is not None), lambda t: run(t, final=False))
-            if tile not in _lib.gemm_tiles("shared"):     # decided for the plain product of the same shape: those tilings have their own epilogues
-                tile = -1
+        if tile == -1:     # (under the key of the plain product of the same shape, whose tilings with an epilogue of their own this form does not have)
+            tile = _tuned(_tuner.key_of(M, N, K, act, odt, bias is not None, residual is not None), lambda t: run(t, final=False), "shared",
+                          lambda: _lib.gemm_candidates("shared", M, N, K, ACT[act], odt, bias is not None, residual is not None))
         run(tile)
         return out
-    if tile == -1 and M <= 4 and colscale is None:
-        tile = 40   # decode step: a weight stream, not a tiled product (gemv_kernel)
-    if tile == -1 and M * N * K >= (1 << 24) and not (residual is not None and residual.data_ptr() == out.data_ptr()):
-        # few output tiles over a very long K (weight gradients dW = dY^T X): also try the split-K form
-        plain = act == "none" and residual is None and colscale is None
-        extra = (25,) if (M * N <= (1 << 20) and K >= 4096 and plain) else ()
-        if plain and bias is None and N % 8 == 0 and M * N <= (1 << 19) and K >= 512:   # skinny products (LoRA x A^T, dY B): 64 x 64 tiles with a K split
-            extra = extra + (14,)
-        if M <= 16 and colscale is None and out_dtype == torch.bfloat16 and act != "swiglu":   # token rows (smaller products take tile 41 without asking)
-            extra = extra + (41,)
-        if act == "none" and N % 192 == 0 and N % 256 != 0 and M >= 1024:   # widths of 3 / 9 x 192 (Hiera stage 3): the ping-pong loop on 256 x 192 tiles
-            extra = extra + (23,)
-        tile = _tuner.pick(_tuner.key_of(M, N, K, act, odt, bias is not None, residual is not None), run, extra)
+    # Not tuned: decode steps (M <= 4 without a column scale: a weight stream, not a tiled product -- the library runs gemv_kernel when asked for -1), products below
+    # the work threshold, and a residual that is the output itself (every trial launch would add it again).
+    if tile == -1 and not (M <= 4 and colscale is None) and M * N * K >= _TUNE_WORK and not (residual is not None and residual.data_ptr() == out.data_ptr()):
+        tile = _tuner.pick(_tuner.key_of(M, N, K, act, odt, bias is not None, residual is not None), run,
+                           lambda: _lib.gemm_candidates("plain", M, N, K, ACT[act], odt, bias is not None, residual is not None, colscale is not None))
     run(tile)
     return out
 
@@ -188,10 +189,9 @@ def gemm_swiglu_pre(a, w, bias=None, tile: int = -1):
         _lib.check(fn(a.data_ptr(), w.data_ptr(), _ptr(bias), out.data_ptr(), pre.data_ptr(), M, N, K, a.stride(0), w.stride(0), out.stride(0), pre.stride(0), t,
                       ws.data_ptr(), ws.numel(), _stream()), "gemm_swiglu_pre_bf16")
 
-    if tile == -1 and M * N * K >= (1 << 24):
-        tile = _tuner.pick(_tuner.key_of(M, N, K, "swiglu+pre", BF16, bias is not None, False), run)
-        if tile not in _lib.gemm_tiles("shared"):    # forced (tuner.force) tilings with an epilogue of their own: no pre-activation store there
-            tile = -1
+    if tile == -1 and M * N * K >= _TUNE_WORK:     # ("shared": tilings with an epilogue of their own have no pre-activation store)
+        tile = _tuned(_tuner.key_of(M, N, K, "swiglu+pre", BF16, bias is not None, False), run, "shared",
+                      lambda: _lib.gemm_candidates("plain", M, N, K, ACT["swiglu"], BF16, bias is not None))
     run(tile)
     return out, pre
 
@@ -223,9 +223,9 @@ def gemm_cat(a, w, bias=None, a2=None, w2=None, wn=None, tile: int = -1):
                       out_n.stride(0) if out_n is not None else 0, t, _stream()), "gemm_cat_bf16")
 
     if tile == -1:
-        cands = tuple(t for t, bn in _lib.gemm_tiles("cat_k" if wn is None else "cat_n").items() if wn is None or N % bn == 0)
-        tile = _tuner.pick(_tuner.key_of(M, N + N2, K + K2, "cat", BF16, bias is not None, False), run, candidates=cands)
-        if tile not in cands:    # a tiling forced for the plain GEMMs (tuner.force) that this entry point does not have
+        entry = "cat_k" if wn is None else "cat_n"
+        tile = _tuned(_tuner.key_of(M, N + N2, K + K2, "cat", BF16, bias is not None, False), run, entry, lambda: _lib.gemm_candidates(entry, M, N, K, bias=bias is not None))
+        if wn is not None and tile != -1 and N % _lib.gemm_tiles(entry)[tile]:    # forced, or decided for another split of N + N2: with an N side N is whole tile columns
             tile = -1
     run(tile)
     return out if out_n is None else (out, out_n)
@@ -342,15 +342,15 @@ def gemm_lnsum(a, w, bias=None, residual=None, tile: int = -1):
         assert residual.dtype == torch.bfloat16 and residual.shape == (M, N) and residual.stride(1) == 1
         ldr = residual.stride(0)
     L = _lib.load()
-    if tile == -1 and M * N * K >= (1 << 24):
+    if tile == -1 and M * N * K >= _TUNE_WORK:
         ws = gemm_workspace(a.device)
 
         def trial(t):      # the plain kernel of the same tiling (same main loop; the tuner only ranks tilings)
             _lib.check(L.rga3_gemm_bf16(a.data_ptr(), w.data_ptr(), _ptr(bias), _ptr(residual), None, out.data_ptr(), M, N, K, a.stride(0), w.stride(0), out.stride(0), ldr,
                                         ACT["none"], BF16, t, ws.data_ptr(), ws.numel(), _stream()), "gemm_bf16")
 
-        cands = tuple(t for t in _lib.gemm_tiles("lnsum") if t != 23 or (N % 192 == 0 and N % 256 != 0 and M >= 1024))
-        tile = _tuner.pick(_tuner.key_of(M, N, K, "lnsum", BF16, bias is not None, residual is not None), trial, candidates=cands)
+        tile = _tuner.pick(_tuner.key_of(M, N, K, "lnsum", BF16, bias is not None, residual is not None), trial,
+                           lambda: _lib.gemm_candidates("lnsum", M, N, K, bias=bias is not None, residual=residual is not None))
     if tile not in _lib.gemm_tiles("lnsum"):
         tile = -1
     ns = int(L.rga3_gemm_lnsum_slices(N, tile))
@@ -389,16 +389,17 @@ def gemm_ln(a, stats, wf, colc, biasf, act: str = "none", out=None, tile: int = 
             _lib.check(fn(a.data_ptr(), wf.data_ptr(), _ptr(biasf), colc.data_ptr(), stats.data_ptr(), out.data_ptr(), M, N, K, a.stride(0), wf.stride(0), out.stride(0),
                           ACT[act], t, _stream()), "gemm_ln_bf16")
 
-    if tile == -1 and M * N * K >= (1 << 24):
-        tile = _tuner.pick(_tuner.key_of(M, N, K, "ln+" + act, BF16, biasf is not None, False), run, candidates=tuple(_lib.gemm_tiles("ln")))
-        if tile not in _lib.gemm_tiles("ln"):    # a tiling forced for the plain GEMMs (tuner.force) that this entry point does not have
-            tile = -1
+    if tile == -1 and M * N * K >= _TUNE_WORK:
+        tile = _tuned(_tuner.key_of(M, N, K, "ln+" + act, BF16, biasf is not None, False), run, "ln", lambda: _lib.gemm_candidates("ln", M, N, K, ACT[act], bias=biasf is not None))
     run(tile)
     return out
 
 
 def gemm_tn(a: torch.Tensor, b: torch.Tensor, out_dtype=torch.bfloat16, out=None, fused_sum: bool = False) -> torch.Tensor:
-    """out [M, N] = a^T @ b for a [K, M], b [K, N] bf16 (row stride free): dW = dY^T X without transposing either operand."""
+    """out [M, N] = a^T @ b for a [K, M], b [K, N] bf16 (row stride free): dW = dY^T X without transposing either operand.  Few output tiles over many tokens are cut
+    into the K slices the library's one rule gives (rga3_gemm_tn_slices, as gemm_tn_many).  Until that rule was the only one this wrapper sized the workspace by a
+    formula of its own, which agreed with it for every K % 32 == 0 but left K = 993 .. 1023 unsplit and bought one slab too few for K >= 1024 with K % 256 > 224: there
+    the partition of K, and with it the f32 summation order, is now the library's."""
     _need_cuda(a, b, out)
     assert a.dtype == torch.bfloat16 and b.dtype == torch.bfloat16 and a.dim() == 2 and b.dim() == 2 and a.shape[0] == b.shape[0]
     assert a.stride(1) == 1 and b.stride(1) == 1
@@ -410,9 +411,9 @@ def gemm_tn(a: torch.Tensor, b: torch.Tensor, out_dtype=torch.bfloat16, out=None
         out = torch.empty((M, N), dtype=out_dtype, device=a.device)
     assert out.shape == (M, N) and out.stride(1) == 1 and out.dtype == out_dtype
     ws = cnt = None
-    tiles = ((M + 127) // 128) * ((N + 127) // 128)
-    if tiles < 128 and K >= 1024:      # few output tiles over many tokens: give the kernel room to split K (<= 64 f32 slabs)
-        ws = torch.empty((min(64, 256 // tiles, max(2, K // 256)) * M * N,), dtype=torch.float32, device=a.device)
+    slabs = _lib.gemm_tn_slices(M, N, K)
+    if slabs > 1:      # few output tiles over many tokens: give the kernel room to split K (<= 64 f32 slabs)
+        ws = torch.empty((slabs * M * N,), dtype=torch.float32, device=a.device)
         if fused_sum:
             cnt = _tn_counters(a.device)[:128]
         # (cnt stays None by default: the in-launch slab sum -- last workgroup per tile, rga3_gemm_tn_bf16's `counters` -- was measured 3x SLOWER than the second launch it saves:
@@ -440,10 +441,7 @@ def gemm_tn_many(pairs, out_dtype=torch.bfloat16):
         N = b.shape[1]
         out = torch.empty((M, N), dtype=out_dtype, device=a.device)
         outs.append(out)
-        tiles = ((M + 127) // 128) * ((N + 127) // 128)
-        nk = (K + 31) // 32
-        z = max(1, min(64, 256 // tiles, nk // 8)) if (tiles < 128 and nk >= 32) else 1
-        need += z * M * N
+        need += _lib.gemm_tn_slices(M, N, K) * M * N
         for j, t in enumerate((a, b, out)):
             ptrs[3 * i + j] = t.data_ptr()
         for j, v in enumerate((M, N, K, a.stride(0), b.stride(0), out.stride(0), BF16 if out_dtype == torch.bfloat16 else F32)):

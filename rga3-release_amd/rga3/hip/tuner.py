@@ -14,9 +14,6 @@ import os
 
 import torch
 
-CANDIDATES = (20, 21, 22, 27, 28, 31, 32, 12, 13, 3, 4, 5, 6)   # 256x256 ping-pong: one tile per workgroup / persistent / persistent + stream-K tail / persistent with the ragged-row loop; 28 = 256x256 on four waves;
-                                               # 192x256 persistent / + stream-K tail (M = 2112 = 11 x 192); single-phase 128x128, 64x64,
-                                               # 128x256, 128x320, 128x192; 128x256 with three LDS stages (two K-tiles in flight)
 _cache = {}
 _times = {}   # key -> {tile: ms of 3 launches} (diagnostic, see table())
 _enabled = os.environ.get("RGA3_GEMM_TUNE", "1") != "0"
@@ -48,8 +45,9 @@ def key_of(M, N, K, act, out_f32, has_bias, has_res):
     return ((M + 255) // 256, N, K, act, out_f32, has_bias, has_res)
 
 
-def pick(key, run, extra=(), candidates=None):
-    """run(tile) launches the GEMM once with that tiling.  Returns the cached / measured best tile id."""
+def pick(key, run, candidates):
+    """run(tile) launches the GEMM once with that tiling; candidates() lists the tilings to time, in trial order (the first of equal times wins) -- which tilings those
+    are is the library's rule (rga3.hip.lib.gemm_candidates), asked only when the shape has to be measured.  Returns the cached / measured best tile id."""
     if _forced[0] is not None:
         return _forced[0]
     if not _enabled:
@@ -61,7 +59,7 @@ def pick(key, run, extra=(), candidates=None):
         return -1
     best, best_ms = -1, float("inf")
     _times[key] = {}
-    for tile in tuple(CANDIDATES if candidates is None else candidates) + tuple(extra):
+    for tile in candidates():
         run(tile)  # warm (also sets the func attribute for large dynamic LDS)
         st, en = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         st.record()

@@ -483,7 +483,7 @@ def test_gemm_tn(dev, form, K, f32, pad):
 @pytest.mark.parametrize("pad", PADS)
 def test_gemm_tn_many(dev, pad):
     """rga3_gemm_tn_many (test_gemm_tn_many_equals_single_products: bit-identical to the single form, 6e-3): every A, B and C a view."""
-    from rga3.hip import ops
+    from rga3.hip import lib, ops
 
     shapes = [(1024, 136, 72), (300, 8, 264)]
     pairs = [(_rand((K, M), dev, seed=K), _rand((K, N), dev, seed=K + 1)) for K, M, N in shapes]
@@ -494,8 +494,7 @@ def test_gemm_tn_many(dev, pad):
     n = len(shapes)
     ptrs, dims, need = (C.c_void_p * (3 * n))(), (C.c_int64 * (7 * n))(), 0
     for i, ((K, M, N), (a, b), o) in enumerate(zip(shapes, views, outs)):
-        tiles, nk = ((M + 127) // 128) * ((N + 127) // 128), (K + 31) // 32
-        need += (max(1, min(64, 256 // tiles, nk // 8)) if (tiles < 128 and nk >= 32) else 1) * M * N
+        need += lib.gemm_tn_slices(M, N, K) * M * N
         ptrs[3 * i], ptrs[3 * i + 1], ptrs[3 * i + 2] = a.data_ptr(), b.data_ptr(), o.data_ptr()
         for j, v in enumerate((M, N, K, a.stride(0), b.stride(0), o.stride(0), 0)):
             dims[7 * i + j] = v

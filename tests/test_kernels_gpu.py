@@ -345,7 +345,9 @@ def test_attn_causal32_rope_on_load(dev, S, Hq, Hkv):
 
 def test_gemm_tn_many_equals_single_products(dev):
     """rga3_gemm_tn_many: the four LoRA weight-gradient products of a decoder layer (dA_q, dB_q, dA_v, dB_v; autograd of PEFT's lora_A / lora_B, reference
-    train_joint.py:193-232) in one launch, bit-identical to rga3_gemm_tn_bf16 on each pair (same K split, same slab order), strided operands included."""
+    train_joint.py:193-232) in one launch, bit-identical to rga3_gemm_tn_bf16 on each pair (same K split, same slab order), strided operands included.  K is a token
+    count: the small products take K = 1000 (31.25 K-tiles of 32, below the 1024 at which the single form once began to split) and K = 1272 (K % 256 > 224: 39.75 K-tiles,
+    5 slices of 8), where a second copy of the slice rule in the wrapper of the single form had drifted from the library's, beside K = 1024 where both agreed."""
     from rga3.hip import ops
 
     T, H, r = 2112, 3584, 128
@@ -362,6 +364,87 @@ def test_gemm_tn_many_equals_single_products(dev):
     assert torch.equal(o2[1], ops.gemm_tn(pairs[1][0], pairs[1][1], out_dtype=torch.float32))
     o3 = ops.gemm_tn_many([(dtq[:, :20], h1)])          # ragged width: falls back to the single form
     assert o3[0].shape == (20, H)
+    small = [(_rand((K, M), dev, seed=20 + i), _rand((K, N), dev, seed=30 + i)) for i, (K, M, N) in enumerate([(1000, 128, 128), (1272, 128, 128), (1272, 128, 256), (1024, 128, 128)])]
+    for odt, tol in ((torch.bfloat16, 6e-3), (torch.float32, 2e-5)):
+        for (a, b), o in zip(small, ops.gemm_tn_many(small, out_dtype=odt)):
+            assert torch.equal(o, ops.gemm_tn(a, b, out_dtype=odt)), (a.shape, b.shape, odt)
+            assert _rel_l2(o, a.float().cpu().t() @ b.float().cpu()) < tol, (a.shape, b.shape, odt)
+
+
+def test_tuner_times_the_tilings_the_library_lists(dev, monkeypatch):
+    """Which tilings a wrapper's first call times, and in which order (tuner.pick keeps the first of equal times): the literal lists of tests/test_gemm_tiles.py, read
+    back from tuner.timings() -- the `extra` tilings of ops.gemm on both sides of their predicates, gemm_lnsum with and without the 256 x 192 tiling (M = 1024 / 1008),
+    gemm_cat with an N side at a width only the 64-wide tiling divides.  The winner is passed on and accepted, a second call times nothing, and the result equals the
+    tile = 12 one.  Bounds (rel-L2, both sides bf16 roundings of f32 sums that differ in summation order only): gemm 1e-3 as test_gemm_streamk_* against tile 20, 2e-3 for
+    token rows (M <= 16) as test_gemm_token_rows against tile 12; gemm_swiglu_pre 1e-4 on the pre-activations as test_gemm_swiglu_with_preactivations, its activations as
+    gemm; gemm_lnsum 1e-2 as test_layernorm_sums_out_of_the_producer_epilogue (tuned against 12); gemm_ln and gemm_cat have no tile-against-tile bound there: theirs are
+    the main loops of gemm behind another epilogue, hence gemm's 1e-3 (gemm_cat against the two plain products it fuses, as test_gemm_concatenated_operands)."""
+    from rga3.hip import ops, tuner
+
+    monkeypatch.setattr(tuner, "_enabled", True)
+    monkeypatch.setattr(tuner, "_forced", [None])
+    base = [20, 21, 22, 27, 28, 31, 32, 12, 13, 3, 4, 5, 6]
+    BF = 0
+
+    def close(got, want, tol):
+        got, want = (got, want) if isinstance(got, tuple) else ((got,), (want,))
+        tol = tol if isinstance(tol, tuple) else (tol,) * len(got)
+        for g, w, t in zip(got, want, tol):
+            assert _rel_l2(g, w.float().cpu()) < t, (t, _rel_l2(g, w.float().cpu()))
+
+    def tuned(key, want, call, ref, tol):
+        old = (tuner._cache.pop(key, None), tuner._times.pop(key, None))
+        try:
+            out = call()
+            assert list(tuner.timings()[key]) == want, (key, list(tuner.timings()[key]))
+            assert tuner.table()[key] in want
+            n, times = len(tuner._times), tuner._times[key]
+            call()
+            assert len(tuner._times) == n and tuner._times[key] is times and list(times) == want       # nothing re-tuned
+            close(out, ref(), tol)
+        finally:
+            for d, v in zip((tuner._cache, tuner._times), old):
+                d.pop(key, None)
+                if v is not None:
+                    d[key] = v
+
+    a, w = _rand((64, 4096), dev, seed=1), _rand((64, 4096), dev, 0.02, seed=2)
+    tuned(tuner.key_of(64, 64, 4096, "none", BF, False, False), base + [25, 14], lambda: ops.gemm(a, w), lambda: ops.gemm(a, w, tile=12), 1e-3)
+    a, w = _rand((16, 1024), dev, seed=3), _rand((1024, 1024), dev, 0.03, seed=4)
+    tuned(tuner.key_of(16, 1024, 1024, "none", BF, False, False), base + [14, 41], lambda: ops.gemm(a, w), lambda: ops.gemm(a, w, tile=12), 2e-3)
+
+    a, w = _rand((64, 1024), dev, seed=5), _rand((256, 1024), dev, 0.03, seed=6)
+
+    def rms(tile):
+        sums = torch.zeros(64, dtype=torch.int64, device=dev)
+        out = ops.gemm(a, w, tile=tile, rms_out=sums)
+        ss = (out.double() ** 2).sum(1)
+        assert ((sums.double() / 2 ** 20 - ss).abs() / ss).max().item() < 1e-5      # the trial launches added nothing to the caller's row sums
+        return out
+    tuned(tuner.key_of(64, 256, 1024, "none", BF, False, False), base, lambda: rms(-1), lambda: rms(12), 1e-3)
+
+    a, w, b = _rand((256, 256), dev, seed=7), _rand((256, 256), dev, 0.06, seed=8), _rand((256,), dev, 0.3, seed=9)
+    tuned(tuner.key_of(256, 256, 256, "swiglu+pre", BF, True, False), base, lambda: ops.gemm_swiglu_pre(a, w, b), lambda: ops.gemm_swiglu_pre(a, w, b, tile=12), (1e-3, 1e-4))
+
+    st = ops.layernorm_stats(a, 1e-6)
+    gamma, beta = _rand((256,), dev, 0.2, seed=10) + 1, _rand((256,), dev, 0.1, seed=11)
+    wf, colc, bfold = ops.fold_layernorm(w, b, gamma, beta)
+    tuned(tuner.key_of(256, 256, 256, "ln+gelu", BF, True, False), [20, 3, 5, 12, 13, 6, 7], lambda: ops.gemm_ln(a, st, wf, colc, bfold, act="gelu"),
+          lambda: ops.gemm_ln(a, st, wf, colc, bfold, act="gelu", tile=12), 1e-3)
+
+    w = _rand((576, 64), dev, 0.12, seed=12)
+
+    def lnsum(tile):
+        out, parts = ops.gemm_lnsum(a, w, tile=tile)
+        of = out.double().cpu()
+        assert float((parts[:, :, 0].double().sum(1).cpu() - of.sum(1)).abs().max()) <= 2e-5 * float(of.abs().sum(1).max())      # the partial sums are those of the tiling that ran
+        return out
+    for M, want in ((1024, [20, 3, 5, 12, 13, 23]), (1008, [20, 3, 5, 12, 13])):      # one key (M in buckets of 256): dropped before each
+        a = _rand((M, 64), dev, seed=13)
+        tuned(tuner.key_of(M, 576, 64, "lnsum", BF, False, False), want, lambda: lnsum(-1), lambda: lnsum(12), 1e-2)
+
+    dy, wt, wn = _rand((256, 64), dev, seed=14), _rand((576, 64), dev, 0.12, seed=15), _rand((64, 64), dev, 0.12, seed=16)
+    tuned(tuner.key_of(256, 576 + 64, 64, "cat", BF, False, False), [13], lambda: ops.gemm_cat(dy, wt, wn=wn), lambda: (ops.gemm(dy, wt, tile=12), ops.gemm(dy, wn, tile=12)), 1e-3)
 
 
 @pytest.mark.parametrize("tile", [-1, 3, 6, 12, 13])

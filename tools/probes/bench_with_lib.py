@@ -15,10 +15,9 @@ if suffix != "-":
     import torch  # noqa: F401  (its HIP runtime first: the library must bind to that one)
     _lib.LIB_PATH = os.path.join(ROOT, "rga3-release_amd", f"librga3_hip_{suffix}.so")
     so = ctypes.CDLL(_lib.LIB_PATH)
-    for name in [n for n in _lib.SIGNATURES if not hasattr(so, n)]:     # an older build lacks the entry points (and tilings) added since
+    if not hasattr(so, "rga3_gemm_candidates"):     # the tuner times what the library lists: a build from before that query cannot be driven by these wrappers
+        sys.exit(f"{_lib.LIB_PATH} has no rga3_gemm_candidates: too old for this tree")
+    for name in [n for n in _lib.SIGNATURES if not hasattr(so, n)]:     # an older build lacks the entry points added since
         del _lib.SIGNATURES[name]
-    if not hasattr(so, "rga3_gemm_ragged_plan"):
-        from rga3.hip import tuner as _tuner
-        _tuner.CANDIDATES = tuple(t for t in _tuner.CANDIDATES if t not in (26, 27))
 sys.argv = [os.path.join(ROOT, "bench.py")] + sys.argv[2:]
 runpy.run_path(sys.argv[0], run_name="__main__")

@@ -31,8 +31,8 @@ if variant == "serial":
 if variant == "avoidws":      # tuned picks, but never a tiling that hands partial sums through the workspace (stream-K / split-K)
     _real_pick = tuner.pick
 
-    def _pick(key, run, extra=(), candidates=None):
-        t = _real_pick(key, run, extra, candidates)
+    def _pick(key, run, candidates):
+        t = _real_pick(key, run, candidates)
         if t in (14, 21, 22, 25, 26, 27, 31, 32):
             tm = {k: v for k, v in tuner.timings().get(key, {}).items() if k not in (14, 21, 22, 25, 26, 27, 31, 32)}
             t = min(tm, key=tm.get) if tm else 20
