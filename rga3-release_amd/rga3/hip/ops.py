@@ -11,6 +11,7 @@ import torch
 
 from . import lib as _lib
 from . import tuner as _tuner
+from .derived import derived as _derived
 
 BF16, F32 = 0, 1
 ACT = {"none": 0, "gelu": 1, "swiglu": 2, "relu": 3}
@@ -281,21 +282,14 @@ def fold_layernorm(weight, bias, gamma, beta):
     return wf, colc, bf.to(torch.bfloat16).contiguous()
 
 
-_hm288_packs = {}   # (pointers + versions of the folded operands) -> (packed chunk images, the operands themselves: kept alive so that an address cannot be recycled)
-
-
 def _hiera_mlp288_pack(wf, colc, biasf, w2):
     """The 36 chunk images rga3_hiera_mlp288 streams by LDS-DMA (csrc/hiera_mlp.hip), built once per frozen block."""
-    key = (wf.data_ptr(), wf._version, colc.data_ptr(), colc._version, biasf.data_ptr(), biasf._version, w2.data_ptr(), w2._version)
-    hit = _hm288_packs.get(key)
-    if hit is None:
+    def build():
         L = _lib.load()
         pack = torch.empty(int(L.rga3_hiera_mlp288_pack_bytes()), dtype=torch.uint8, device=wf.device)
         _lib.check(L.rga3_hiera_mlp288_pack(wf.data_ptr(), colc.data_ptr(), biasf.data_ptr(), w2.data_ptr(), pack.data_ptr(), _stream()), "hiera_mlp288_pack")
-        if len(_hm288_packs) > 64:
-            _hm288_packs.clear()
-        hit = _hm288_packs[key] = (pack, (wf, colc, biasf, w2))
-    return hit[0]
+        return pack
+    return _derived(None, "hiera_mlp288", wf, colc, biasf, w2, build=build)
 
 
 def hiera_mlp(x, wf, colc, biasf, w2, b2, eps: float):
@@ -694,9 +688,6 @@ def bilinear(x, size, plane_idx=None):
     return out
 
 
-_conv_pack = {}
-
-
 def decimg_rows(keys, pe, kt, vt, nk: int, q_proj, out_proj, norm, eps: float, k_next=None, v_next=None, scale: float = 0.25, v_transposed: bool = False):
     """The image side of a mask-decoder block boundary in one launch (csrc/decimg.hip): keys [M, 256], pe [hw, 256] (broadcast over frames), kt / vt [frames * nk, 128]
     token-side keys / values (projected), q_proj / out_proj / k_next / v_next = (weight, bias) pairs, norm = (weight, bias).  -> (keys', k2, v2) (k2 = v2 = None
@@ -786,12 +777,7 @@ def conv3x3s2(x, weight, bias, F: int, H: int, W: int, sig_scale: float = 0.0, s
     assert weight.dtype == torch.bfloat16 and weight.is_contiguous() and x.is_contiguous() and x.numel() == F * H * W * Cin
     if x.dtype == torch.bfloat16 and Cin % 8 == 0 and Cin >= 16:
         # wide stages: im2col (16-byte copies) + the NT GEMM on the weight repacked [Cout, (kh, kw, ci)] (cached per weight version)
-        key = (weight.data_ptr(), weight._version)
-        wp = _conv_pack.get(key)
-        if wp is None:
-            if len(_conv_pack) > 64:
-                _conv_pack.clear()
-            wp = _conv_pack[key] = weight.detach().permute(0, 2, 3, 1).reshape(Cout, 9 * Cin).contiguous()
+        wp = _derived(None, "conv3x3s2", weight, build=lambda: weight.detach().permute(0, 2, 3, 1).reshape(Cout, 9 * Cin).contiguous())
         cols = torch.empty((F * (H // 2) * (W // 2), 9 * Cin), dtype=torch.bfloat16, device=x.device)
         _lib.check(_lib.load().rga3_im2col3x3s2(x.data_ptr(), cols.data_ptr(), F, H, W, Cin, _stream()), "im2col3x3s2")
         return gemm(cols, wp, bias)

@@ -33,6 +33,7 @@ import torch
 import torch.nn as nn
 
 from ..hip import ops
+from ..hip.derived import derived
 from ..utils.staging import host_of, upload
 from . import qwen_index as QI
 
@@ -172,10 +173,6 @@ def _is_plain(*mods):
     return all(type(m) is Linear for m in mods)
 
 
-def _versions(*params):
-    return tuple((p.data_ptr(), p._version, p.dtype) for p in params if p is not None)
-
-
 # RMSNorm folded into the products on either side of it (inference / frozen towers only): the residual-producing projection (o_proj, down_proj, the ViT's proj /
 # fc2) leaves the row sums of squares of what it writes (rga3_gemm_rms_bf16, rms_out), the projection that consumes the normalised rows (q|k|v, gate|up) takes the
 # UN-normalised rows with the norm weight folded into its weight and scales its accumulators by 1 / rms (rms_in).  The stand-alone norm launch and the write +
@@ -224,34 +221,30 @@ class GatedMLP(nn.Module):
         self.gate_proj = Linear(hidden, inter, bias=bias)
         self.up_proj = Linear(hidden, inter, bias=bias)
         self.down_proj = Linear(inter, hidden, bias=bias)
-        self._pk = None
+
+    def _pack_srcs(self):
+        return self.gate_proj.weight, self.up_proj.weight, self.down_proj.weight, self.gate_proj.bias, self.up_proj.bias
 
     def _packed(self):
-        key = _versions(self.gate_proj.weight, self.up_proj.weight, self.down_proj.weight, self.gate_proj.bias, self.up_proj.bias)
-        if self._pk is None or self._pk[0] != key:
+        def build():
             I = self.gate_proj.out_features
             Ip = (I + 63) // 64 * 64  # K of the down GEMM must be a multiple of 64
-            with torch.no_grad():
-                wgu = _interleave_rows(self.gate_proj.weight.detach(), self.up_proj.weight.detach(), Ip)
-                bgu = None
-                if self.gate_proj.bias is not None:
-                    bgu = _interleave_rows(self.gate_proj.bias.detach(), self.up_proj.bias.detach(), Ip)
-                wd = self.down_proj.weight.detach()
-                if Ip != I:
-                    wd = torch.cat([wd, torch.zeros((wd.shape[0], Ip - I), dtype=wd.dtype, device=wd.device)], dim=1).contiguous()
-            self._pk = (key, wgu, bgu, wd)
-        return self._pk[1:]
+            wgu = _interleave_rows(self.gate_proj.weight.detach(), self.up_proj.weight.detach(), Ip)
+            bgu = None
+            if self.gate_proj.bias is not None:
+                bgu = _interleave_rows(self.gate_proj.bias.detach(), self.up_proj.bias.detach(), Ip)
+            wd = self.down_proj.weight.detach()
+            if Ip != I:
+                wd = torch.cat([wd, torch.zeros((wd.shape[0], Ip - I), dtype=wd.dtype, device=wd.device)], dim=1).contiguous()
+            return wgu, bgu, wd
+        return derived(self, "pack", *self._pack_srcs(), build=build)
 
     def _packed_folded(self, norm):
         """gate|up pack with the preceding RMSNorm's weight folded in (W diag(gamma), one bf16 rounding), rebuilt when a source changes."""
-        wgu, _, _ = self._packed()
-        key = (self._pk[0], _versions(norm.weight))
-        pf = self.__dict__.get("_pkf")
-        if pf is None or pf[0] != key:
-            with torch.no_grad():
-                pf = (key, (wgu.float() * norm.weight.detach().float()[None, :]).to(wgu.dtype).contiguous())
-            self.__dict__["_pkf"] = pf
-        return pf[1]
+        def build():
+            wgu = self._packed()[0]
+            return (wgu.float() * norm.weight.detach().float()[None, :]).to(wgu.dtype).contiguous()
+        return derived(self, "pack:fold", *self._pack_srcs(), norm.weight, build=build)
 
     def forward(self, x2d, residual, fold=None, rms_out=None):
         """fold = (norm module, row sums of squares of x2d): x2d is then the UN-normalised row block (== residual) and the norm is applied inside the gate|up product."""
@@ -276,16 +269,15 @@ class VisionPatchEmbed(nn.Module):
         super().__init__()
         k = (c.temporal_patch_size, c.patch_size, c.patch_size)
         self.proj = nn.Conv3d(c.in_channels, c.hidden_size, kernel_size=k, stride=k, bias=False)  # parameter container only
-        self._pk = None
 
     def forward(self, px):
         w = self.proj.weight
-        key = _versions(w)
-        if self._pk is None or self._pk[0] != key:
+
+        def build():
             w2 = w.detach().reshape(w.shape[0], -1)
             kp = (w2.shape[1] + 63) // 64 * 64
-            self._pk = (key, ops.pad_cols(w2.contiguous(), kp) if kp != w2.shape[1] else w2.contiguous())
-        wp = self._pk[1]
+            return ops.pad_cols(w2.contiguous(), kp) if kp != w2.shape[1] else w2.contiguous()
+        wp = derived(self, "pack", w, build=build)
         if px.shape[1] != wp.shape[1]:
             px = ops.pad_cols(px, wp.shape[1])
         return ops.gemm(px, wp)
@@ -300,13 +292,8 @@ class VisionAttention(nn.Module):
         self.proj = Linear(c.hidden_size, c.hidden_size, bias=True)
 
     def _qkv_folded(self, norm):
-        key = _versions(self.qkv.weight, norm.weight)
-        pf = self.__dict__.get("_pkf")
-        if pf is None or pf[0] != key:
-            with torch.no_grad():
-                pf = (key, (self.qkv.weight.detach().float() * norm.weight.detach().float()[None, :]).to(self.qkv.weight.dtype).contiguous())
-            self.__dict__["_pkf"] = pf
-        return pf[1]
+        w = self.qkv.weight
+        return derived(self, "wqkv:fold", w, norm.weight, build=lambda: (w.detach().float() * norm.weight.detach().float()[None, :]).to(w.dtype).contiguous())
 
     def forward(self, h, residual, cu, max_len, cos, sin, fold=None, rms_out=None):
         N = h.shape[0]
@@ -468,27 +455,19 @@ class DecoderAttention(nn.Module):
         self.k_proj = Linear(hs, self.num_kv * self.head_dim, bias=True)
         self.v_proj = Linear(hs, self.num_kv * self.head_dim, bias=True)
         self.o_proj = Linear(self.num_heads * self.head_dim, hs, bias=False)
-        self._pk = None
+
+    def _pack_srcs(self):
+        return self.q_proj.weight, self.k_proj.weight, self.v_proj.weight, self.q_proj.bias, self.k_proj.bias, self.v_proj.bias
 
     def _packed(self):
-        ps = (self.q_proj.weight, self.k_proj.weight, self.v_proj.weight, self.q_proj.bias, self.k_proj.bias, self.v_proj.bias)
-        key = _versions(*ps)
-        if self._pk is None or self._pk[0] != key:
-            with torch.no_grad():
-                w = torch.cat([p.detach() for p in ps[:3]]).contiguous()
-                b = torch.cat([p.detach() for p in ps[3:]]).contiguous()
-            self._pk = (key, w, b)
-        return self._pk[1:]
+        ps = self._pack_srcs()
+        return derived(self, "pack", *ps, build=lambda: (torch.cat([p.detach() for p in ps[:3]]).contiguous(), torch.cat([p.detach() for p in ps[3:]]).contiguous()))
 
     def _packed_folded(self, norm):
-        w, _ = self._packed()
-        key = (self._pk[0], _versions(norm.weight))
-        pf = self.__dict__.get("_pkf")
-        if pf is None or pf[0] != key:
-            with torch.no_grad():
-                pf = (key, (w.float() * norm.weight.detach().float()[None, :]).to(w.dtype).contiguous())
-            self.__dict__["_pkf"] = pf
-        return pf[1]
+        def build():
+            w = self._packed()[0]
+            return (w.float() * norm.weight.detach().float()[None, :]).to(w.dtype).contiguous()
+        return derived(self, "pack:fold", *self._pack_srcs(), norm.weight, build=build)
 
     def forward(self, h, residual, cos, sin, cu, max_len, cache=None, fold=None, rms_out=None):
         T = h.shape[0]

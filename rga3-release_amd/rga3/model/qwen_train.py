@@ -20,9 +20,10 @@ import torch
 import torch.nn as nn
 
 from ..hip import ops
+from ..hip.derived import derived as _wt      # cached derived tensor keyed by the versions of its sources (frozen weights never change -> built once)
 from ..utils.staging import upload
 from . import qwen2_5_vl as _Q
-from .qwen2_5_vl import GatedMLP, Linear, _versions
+from .qwen2_5_vl import GatedMLP, Linear
 
 
 # ------------------------------------------------------------------------------------------------ LoRA
@@ -72,18 +73,6 @@ def add_lora(model: nn.Module, r=128, alpha=256, dropout=0.0, targets=("q_proj",
             setattr(parent, parts[-1], LoRALinear(mod, r, alpha, dropout))
             hits.append(name)
     return hits
-
-
-# ------------------------------------------------------------------------------------------------ transposed weight packs
-def _wt(owner, key, *srcs, build):
-    """Cached derived tensor keyed by the versions of its sources (frozen weights never change -> built once)."""
-    cache = owner.__dict__.setdefault("_wt_cache", {})
-    ver = _versions(*srcs)
-    hit = cache.get(key)
-    if hit is None or hit[0] != ver:
-        with torch.no_grad():
-            cache[key] = (ver, build())
-    return cache[key][1]
 
 
 # ------------------------------------------------------------------------------------------------ fp8 frozen-weight GEMMs (config 5)
@@ -417,16 +406,9 @@ def _layer_forward_store(layer, x, cos, sin, cu, max_len, seeds):
     return y, (h1, qkv, att, lse, x1, h2, gu, tq, tv, hq_in, hv_in)
 
 
-_neg = {}
-
-
 def _neg_table(sin):
     """-sin, made once per table (every layer's backward un-rotates with the same one)."""
-    key = (sin.data_ptr(), sin._version, tuple(sin.shape))
-    if _neg.get("key") != key:
-        _neg["key"], _neg["t"] = key, (-sin).contiguous()
-        _neg["src"] = sin          # keeps the source alive: its address cannot be reused while the entry exists
-    return _neg["t"]
+    return _wt(None, "neg_sin", sin, build=lambda: (-sin).contiguous())
 
 
 class DecoderLayerFn(torch.autograd.Function):

@@ -28,6 +28,7 @@ import torch.nn.functional as F
 
 from ..hip import autograd as AG
 from ..hip import ops
+from ..hip.derived import derived
 from .qwen2_5_vl import Linear
 
 
@@ -178,16 +179,12 @@ class MultiScaleBlock(nn.Module):
         self.mlp = MLP(dim_out, dim_out * 4, dim_out, 2, act="gelu")
         if dim != dim_out:
             self.proj = Linear(dim, dim_out)
-        self._fold_cache = {}
 
     def _folded(self, which):
         """(Wf, colc, biasf) of a projection with the preceding LayerNorm folded in (ops.fold_layernorm), rebuilt when either module's parameters change."""
         lin, norm = {"qkv": (self.attn.qkv, self.norm1), "proj": (getattr(self, "proj", None), self.norm1), "fc1": (self.mlp.layers[0], self.norm2)}[which]
-        key = (lin.weight.data_ptr(), lin.weight._version, None if lin.bias is None else lin.bias._version, norm.weight.data_ptr(), norm.weight._version, norm.bias._version)
-        c = self._fold_cache.get(which)
-        if c is None or c[0] != key:
-            c = self._fold_cache[which] = (key, ops.fold_layernorm(lin.weight, lin.bias, norm.weight, norm.bias))
-        return c[1]
+        srcs = (lin.weight, lin.bias, norm.weight, norm.bias)
+        return derived(self, "fold:" + which, *srcs, build=lambda: ops.fold_layernorm(*srcs))
 
     def forward(self, x, Fn, H, W, layout_w, sums=None):
         """x [Fn*H*W, dim] in window-major(layout_w) order. Returns (x, H, W, layout_w).
@@ -302,18 +299,15 @@ class Hiera(nn.Module):
             self.blocks.append(MultiScaleBlock(dim, dim_out, heads, window, i in self.q_pool_blocks))
             dim = dim_out
         self.channel_list = [self.blocks[i].dim_out for i in self.stage_ends[::-1]]
-        self._pos_cache = {}
 
     def pos_tokens(self, h, w):
         """bicubic-interpolated background pos-embed + tiled window embed as raster tokens [h*w, C] (sam2.py:1218-1226)."""
-        key = (h, w, self.pos_embed._version, self.pos_embed.device)
-        if key not in self._pos_cache:
-            with torch.no_grad():
-                pe = F.interpolate(self.pos_embed.float(), size=(h, w), mode="bicubic")
-                we = self.pos_embed_window.float()
-                pe = pe + we.tile([a // b for a, b in zip(pe.shape, we.shape)])
-                self._pos_cache = {key: pe[0].permute(1, 2, 0).reshape(h * w, -1).to(self.pos_embed.dtype).contiguous()}
-        return self._pos_cache[key]
+        def build():
+            pe = F.interpolate(self.pos_embed.float(), size=(h, w), mode="bicubic")
+            we = self.pos_embed_window.float()
+            pe = pe + we.tile([a // b for a, b in zip(pe.shape, we.shape)])
+            return pe[0].permute(1, 2, 0).reshape(h * w, -1).to(self.pos_embed.dtype).contiguous()
+        return derived(self, "pos_tokens", self.pos_embed, self.pos_embed_window, build=build, extra=(h, w))
 
     def forward(self, img):
         """img [Fn, 3, S, S] bf16 -> list of (tokens [Fn*H*W, C] raster order, H, W) per stage (high-res first)."""
@@ -544,13 +538,10 @@ class ConvTParams(nn.Module):
         self.weight = nn.Parameter(torch.empty(cin, cout, 2, 2))
         self.bias = nn.Parameter(torch.zeros(cout))
         nn.init.kaiming_uniform_(self.weight, a=math.sqrt(5))
-        self._pk = None
 
     def as_linear(self):
-        key = (self.weight.data_ptr(), self.weight._version, self.weight.dtype)
-        if self._pk is None or self._pk[0] != key:
-            self._pk = (key, self.weight.detach().permute(2, 3, 1, 0).reshape(-1, self.weight.shape[0]).contiguous())
-        return self._pk[1]
+        w = self.weight
+        return derived(self, "as_linear", w, build=lambda: w.detach().permute(2, 3, 1, 0).reshape(-1, w.shape[0]).contiguous())
 
     def as_linear_grad(self):
         """same matrix, recorded by autograd (the permute/reshape are views + one copy that torch differentiates)."""
@@ -588,7 +579,6 @@ class MaskDecoder(nn.Module):
         self.iou_token = nn.Embedding(1, dim)
         self.num_mask_tokens = 4
         self.mask_tokens = nn.Embedding(4, dim)
-        self._tok_cache = None       # (key, tokens) of forward(..., const_sparse=True)
         self.obj_score_token = nn.Embedding(1, dim)
         self.output_upscaling = nn.Sequential(ConvTParams(dim, dim // 4), NormParams(dim // 4, 1e-6), nn.GELU(), ConvTParams(dim // 4, dim // 8), nn.GELU())
         self.conv_s0 = ConvParams(dim // 8, dim, 1, 1)
@@ -601,19 +591,17 @@ class MaskDecoder(nn.Module):
         """pix_tokens [B*h*w, C] (already + dense prompt), pos_tokens [h*w, C], sparse [B, n, C] (const_sparse: it is the prompt encoder's padding alone).
         Returns masks f32 [B, 4, 4h, 4w], iou [B, 4], mask tokens [B, 4, C], object score logits [B, 1]."""
         C = self.transformer_dim
-        tokens = None
+        srcs = (self.obj_score_token.weight, self.iou_token.weight, self.mask_tokens.weight)
+
+        def build():
+            out_tokens = torch.cat(srcs, dim=0)
+            return torch.cat([out_tokens[None].expand(B, -1, -1), sparse.to(out_tokens.dtype)], dim=1).contiguous()
         if const_sparse and not _ag():
             # tracked frames carry no prompt: output tokens + the two padding points are a function of the weights alone -- built once, not with two concatenation
             # launches per frame (a frame of the stream is ~115 dependent launches of >= 4.4 us each)
-            srcs = (self.obj_score_token.weight, self.iou_token.weight, self.mask_tokens.weight, sparse)
-            key = tuple((t_.data_ptr(), t_._version, tuple(t_.shape), t_.dtype) for t_ in srcs) + (B,)
-            if self._tok_cache is not None and self._tok_cache[0] == key:
-                tokens = self._tok_cache[1]
-        if tokens is None:
-            out_tokens = torch.cat([self.obj_score_token.weight, self.iou_token.weight, self.mask_tokens.weight], dim=0)
-            tokens = torch.cat([out_tokens[None].expand(B, -1, -1), sparse.to(out_tokens.dtype)], dim=1).contiguous()
-            if const_sparse and not _ag():
-                self._tok_cache = (key, tokens.detach())
+            tokens = derived(self, "tokens", *srcs, sparse, build=build, extra=B)
+        else:
+            tokens = build()
         nq = tokens.shape[1]
         hs, src = self.transformer(pix_tokens, pos_tokens, tokens.view(B * nq, C), B, nq, h * w)
         hs = hs.view(B, nq, C)
@@ -771,7 +759,6 @@ class MemoryAttention(nn.Module):
         self.d_model = d_model
         self.layers = nn.ModuleList(MemoryAttentionLayer(d_model, dim_feedforward, kv_in_dim) for _ in range(num_layers))
         self.norm = NormParams(d_model, 1e-5)
-        self._pk = None
 
     def _fusable(self):
         return not any(hasattr(m_, "lora_A") for l in self.layers for m_ in (l.self_attn.q_proj, l.self_attn.k_proj, l.self_attn.v_proj, l.self_attn.out_proj,
@@ -780,16 +767,13 @@ class MemoryAttention(nn.Module):
 
     def _packs(self):
         """Derived operands, rebuilt only when a source weight changes (frozen at inference: built once).  Elementwise torch ops + this library's own GEMM."""
-        from .qwen2_5_vl import _versions
         srcs = []
         for l in self.layers:
             for a in (l.self_attn, l.cross_attn_image):
                 for m_ in (a.q_proj, a.k_proj, a.v_proj, a.out_proj):
                     srcs += [m_.weight, m_.bias]
-        ver = _versions(*srcs)
-        if self._pk is not None and self._pk[0] == ver:
-            return self._pk[1]
-        with torch.no_grad():
+
+        def build():
             pk = {"wk_all": torch.cat([l.cross_attn_image.k_proj.weight for l in self.layers], 0).contiguous(),
                   "bk_all": torch.cat([l.cross_attn_image.k_proj.bias for l in self.layers], 0).contiguous(), "layers": []}
             for l in self.layers:
@@ -798,8 +782,8 @@ class MemoryAttention(nn.Module):
                 bov = ops.gemm(ca.v_proj.bias.view(1, -1).contiguous(), ca.out_proj.weight, bias=ca.out_proj.bias, out_dtype=torch.float32).view(-1).to(ca.out_proj.weight.dtype)
                 pk["layers"].append({"wqkv": torch.cat([sa.q_proj.weight, sa.k_proj.weight, sa.v_proj.weight], 0).contiguous(),
                                      "bqkv": torch.cat([sa.q_proj.bias, sa.k_proj.bias, sa.v_proj.bias], 0).contiguous(), "wov": wov.contiguous(), "bov": bov.contiguous()})
-        self._pk = (ver, pk)
-        return pk
+            return pk
+        return derived(self, "packs", *srcs, build=build)
 
     def _tables(self, nq, reps, device):
         """cos / sin of the axial RoPE tiled `reps` times along the columns (one pass rotates `reps` 256-wide column groups of a fused projection)."""
