@@ -514,6 +514,21 @@ int rga3_gemm_fp8(const void* Aq, const void* Wq, const float* sa, const float* 
 int rga3_swiglu_fwd_quant_fp8(const void* gu, void* q, float* scales, int64_t T, int64_t I, void* stream);
 int rga3_swiglu_bwd_quant_fp8(const void* gu, const void* da, void* q, float* scales, int64_t T, int64_t I, void* stream);
 
+/* ---- Weight-only e4m3 for the decode step of generate() (reference app.py:308-317; csrc/gemv_w8.hip): the decoder projections as OCP e4m3 codes with one
+ * power-of-two scale per output row, half the bytes of the bf16 weight stream (rga3_gemm_bf16, tile 40).
+ * q[r, :] = e4m3(w[r, :] / scales[r]) (round to nearest even), scales[r] = 2^k with k the smallest integer such that max|w[r, :]| <= 448 * 2^k, k >= -126
+ * (1 for a zero row).  Every dequantised weight q * 2^k is a bf16 number.  w bf16 [rows, K], K % 16 == 0; ldw in elements (multiple of 8), ldq in BYTES
+ * (multiple of 16); w and q 16-byte aligned. */
+int rga3_quant_e4m3_rows_pow2(const void* w, void* q, float* scales, int64_t rows, int64_t K, int64_t ldw, int64_t ldq, void* stream);
+/* C[M, N_out] = act((A[M,K] . Wq[N,K]^T) * sw[n] + bias[n]) (+ residual), 1 <= M <= 4: A bf16, Wq e4m3 codes, f32 accumulate, bf16 or f32 out.  The epilogue is
+ * tile 40's (bias, bf16 rounding before SiLU, RGA3_ACT_SWIGLU on the 16 / 16 interleaved gate | up row blocks with N_out = N / 2 and N % 32 == 0, the output rounded
+ * to bf16 before the residual is added), so with sums that are exact in f32 the result equals rga3_gemm_bf16's on the dequantised weights bit for bit.
+ * act: RGA3_ACT_NONE or RGA3_ACT_SWIGLU; out_dtype RGA3_F32 takes no residual.  K % 16 == 0; lda / ldc / ldr in elements (lda a multiple of 8), ldw in BYTES
+ * (multiple of 16); A, Wq and C 16-byte aligned.  Stands in for the decoder's q|k|v, o, gate|up and down products (HF modeling_qwen2_5_vl.py:541-553, :602-757)
+ * of a decode step when the model's decode weights are "e4m3". */
+int rga3_gemv_w8(const void* A, const void* Wq, const float* sw, const void* bias, const void* residual, void* C, int64_t M, int64_t N, int64_t K,
+                 int64_t lda, int64_t ldw, int64_t ldc, int64_t ldr, int act, int out_dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

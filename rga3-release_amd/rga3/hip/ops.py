@@ -1119,6 +1119,52 @@ def gemm_fp8(aq, sa, wq, sw, bias=None, residual=None, out=None):
     return out
 
 
+def quant_e4m3_rows_pow2(w, out=None):
+    """bf16 [rows, K] (row stride free, K % 16 == 0) -> (uint8 [rows, K] holding OCP e4m3, f32 scales [rows]): q = e4m3(w / scale) with scale = 2^k, k the
+    smallest integer such that the row's amax <= 448 * 2^k (1 for a zero row), so that q * scale is a bf16 number.  out = (codes, scales) views to write into."""
+    _need_cuda(w)
+    assert w.dtype == torch.bfloat16 and w.dim() == 2 and w.stride(1) == 1
+    rows, K = w.shape
+    if out is None:
+        out = (torch.empty((rows, K), dtype=torch.uint8, device=w.device), torch.empty((rows,), dtype=torch.float32, device=w.device))
+    q, sc = out
+    _need_cuda(q, sc)
+    assert q.dtype == torch.uint8 and q.shape == (rows, K) and q.stride(1) == 1 and sc.dtype == torch.float32 and sc.shape == (rows,) and sc.is_contiguous()
+    _lib.check(_lib.load().rga3_quant_e4m3_rows_pow2(w.data_ptr(), q.data_ptr(), sc.data_ptr(), rows, K, w.stride(0), q.stride(0), _stream()), "quant_e4m3_rows_pow2")
+    return q, sc
+
+
+def dequant_e4m3_rows(q, sc):
+    """bf16 [rows, K] = code * scale of quant_e4m3_rows_pow2's output (exact: every such product is a bf16 number).  Weight preparation, not a hot path."""
+    return (q.view(torch.float8_e4m3fn).float() * sc[:, None]).to(torch.bfloat16)
+
+
+def gemv_w8(a, wq, sw, bias=None, residual=None, act: str = "none", out_dtype=torch.bfloat16, out=None):
+    """out = residual + act((a @ dequant(wq, sw).T) + bias) for 1 <= M <= 4 rows: a [M, K] bf16, wq [N, K] e4m3 codes (uint8), sw [N] f32 row scales.
+    The decode-step weight stream at one byte per weight (rga3_gemv_w8); act "none" or "swiglu" (gate | up rows interleaved 16 / 16, N_out = N / 2)."""
+    _need_cuda(a, wq, sw, bias, residual, out)
+    assert a.dtype == torch.bfloat16 and wq.dtype == torch.uint8 and sw.dtype == torch.float32
+    assert a.dim() == 2 and wq.dim() == 2 and a.shape[1] == wq.shape[1], (a.shape, wq.shape)
+    assert a.stride(1) == 1 and wq.stride(1) == 1 and sw.numel() == wq.shape[0] and sw.is_contiguous()
+    if act not in ACT:
+        raise _lib.Rga3Error(f"gemv_w8: unknown activation {act!r}")
+    M, K = a.shape
+    N = wq.shape[0]
+    n_out = N // 2 if act == "swiglu" else N
+    if out is None:
+        out = torch.empty((M, n_out), dtype=out_dtype, device=a.device)
+    assert out.shape == (M, n_out) and out.stride(1) == 1 and out.dtype == out_dtype
+    if bias is not None:
+        assert bias.dtype == torch.bfloat16 and bias.numel() == N and bias.is_contiguous()
+    ldr = 0
+    if residual is not None:
+        assert residual.dtype == torch.bfloat16 and residual.shape == (M, n_out) and residual.stride(1) == 1
+        ldr = residual.stride(0)
+    _lib.check(_lib.load().rga3_gemv_w8(a.data_ptr(), wq.data_ptr(), sw.data_ptr(), _ptr(bias), _ptr(residual), out.data_ptr(), M, N, K, a.stride(0), wq.stride(0),
+                                        out.stride(0), ldr, ACT[act], BF16 if out_dtype == torch.bfloat16 else F32, _stream()), "gemv_w8")
+    return out
+
+
 def swiglu_fwd_quant(gu):
     """(e4m3 [T, I], scales [T]) of silu(gate) * up, as quant_fp8_rows(swiglu_fwd(gu)) gives them, without the bf16 tensor in between."""
     _need_cuda(gu)

@@ -203,6 +203,11 @@ def _fold_ok(x2d, *mods) -> bool:
     return _RMS_FOLD and not torch.is_grad_enabled() and x2d.shape[0] > 16 and x2d.dtype == torch.bfloat16 and _is_plain(*mods)
 
 
+def _w8_ok(mod, x2d) -> bool:
+    """Decode-step route of a module marked by set_decode_weights("e4m3"): inference only, at most 4 rows (the weight-stream kernel's range)."""
+    return mod.__dict__.get("_decode_w8", False) and not torch.is_grad_enabled() and x2d.shape[0] <= 4 and x2d.dtype == torch.bfloat16
+
+
 def _interleave_rows(g: torch.Tensor, u: torch.Tensor, pad_to: int) -> torch.Tensor:
     """[I, K] gate / up -> [2*Ip, K] with 16-row blocks alternating gate / up (GEMM SwiGLU epilogue layout)."""
     I = g.shape[0]
@@ -246,10 +251,22 @@ class GatedMLP(nn.Module):
             return (wgu.float() * norm.weight.detach().float()[None, :]).to(wgu.dtype).contiguous()
         return derived(self, "pack:fold", *self._pack_srcs(), norm.weight, build=build)
 
+    def _packed_w8(self):
+        """((codes, scales) of the gate|up pack, (codes, scales) of the down pack): e4m3 with a power-of-two scale per row.  Quantising by row commutes with the
+        packing (rows are reordered, the padding is zeros), so these are the codes of the projections themselves."""
+        def build():
+            wgu, _, wd = self._packed()
+            return ops.quant_e4m3_rows_pow2(wgu), ops.quant_e4m3_rows_pow2(wd)
+        return derived(self, "w8:mlp", *self._pack_srcs(), build=build)
+
     def forward(self, x2d, residual, fold=None, rms_out=None):
         """fold = (norm module, row sums of squares of x2d): x2d is then the UN-normalised row block (== residual) and the norm is applied inside the gate|up product."""
         if _is_plain(self.gate_proj, self.up_proj, self.down_proj):
             wgu, bgu, wd = self._packed()
+            if fold is None and rms_out is None and _w8_ok(self, x2d):
+                (qgu, sgu), (qd, sd) = self._packed_w8()
+                a = ops.gemv_w8(x2d, qgu, sgu, bgu, act="swiglu")
+                return ops.gemv_w8(a, qd, sd, self.down_proj.bias, residual=residual)
             if fold is not None:
                 norm, rs = fold
                 a = ops.gemm(x2d, self._packed_folded(norm), bgu, act="swiglu", rms_in=(rs, x2d.shape[1], norm.variance_epsilon))
@@ -469,6 +486,14 @@ class DecoderAttention(nn.Module):
             return (w.float() * norm.weight.detach().float()[None, :]).to(w.dtype).contiguous()
         return derived(self, "pack:fold", *self._pack_srcs(), norm.weight, build=build)
 
+    def _packed_w8(self):
+        """(codes, scales) of the q|k|v pack: e4m3 with a power-of-two scale per row (the rows of the three projections, in order)."""
+        return derived(self, "w8:qkv", *self._pack_srcs(), build=lambda: ops.quant_e4m3_rows_pow2(self._packed()[0]))
+
+    def _o_w8(self):
+        w = self.o_proj.weight
+        return derived(self, "w8:o", w, build=lambda: ops.quant_e4m3_rows_pow2(w.detach()))
+
     def forward(self, h, residual, cos, sin, cu, max_len, cache=None, fold=None, rms_out=None):
         T = h.shape[0]
         Hq, Hk, D = self.num_heads, self.num_kv, self.head_dim
@@ -478,7 +503,10 @@ class DecoderAttention(nn.Module):
             qkv = ops.gemm(h, self._packed_folded(norm), b, rms_in=(rs, h.shape[1], norm.variance_epsilon)).view(T, Hq + 2 * Hk, D)
         elif _is_plain(self.q_proj, self.k_proj, self.v_proj):
             w, b = self._packed()
-            qkv = ops.gemm(h, w, b).view(T, Hq + 2 * Hk, D)
+            if _w8_ok(self, h):
+                qkv = ops.gemv_w8(h, *self._packed_w8(), b).view(T, Hq + 2 * Hk, D)
+            else:
+                qkv = ops.gemm(h, w, b).view(T, Hq + 2 * Hk, D)
         elif all(type(m).__name__ in ("Linear", "LoRALinear") and type(m).__module__.startswith("rga3.") for m in (self.q_proj, self.k_proj, self.v_proj)):
             from .qwen_train import qkv_with_lora  # native LoRA: fused projection + in-place low-rank updates
             qkv = qkv_with_lora(self, h, seeds=getattr(self, "_lora_drop_seeds", None))[0].view(T, Hq + 2 * Hk, D)
@@ -502,6 +530,8 @@ class DecoderAttention(nn.Module):
             att = ops.attn_varlen(q, k, v, cu, cu_k, max_len, D ** -0.5, causal=(max_len > 1))
         if rms_out is not None:
             return ops.gemm(att.view(T, Hq * D), self.o_proj.weight, self.o_proj.bias, residual=residual, rms_out=rms_out)
+        if _is_plain(self.o_proj) and _w8_ok(self, att):
+            return ops.gemv_w8(att.view(T, Hq * D), *self._o_w8(), self.o_proj.bias, residual=residual)
         return self.o_proj(att.view(T, Hq * D), residual=residual)
 
 
@@ -908,6 +938,62 @@ class Qwen2_5_VLForConditionalGeneration(nn.Module):
         row_loss = ops.cross_entropy_rows(logits_p, tgt)
         return row_loss.sum() / max(n, 1)
 
+    # -- decode weights ------------------------------------------------------------------------------------
+    _W8_PROJS = (("self_attn", ("q_proj", "k_proj", "v_proj", "o_proj")), ("mlp", ("gate_proj", "up_proj", "down_proj")))
+
+    def _plain_decoder_projections(self):
+        """[(layer, its seven projections)] of the decoder layers whose projections are all this file's un-wrapped Linear."""
+        out = []
+        for layer in self.model.layers:
+            mods = [getattr(getattr(layer, part), n) for part, names in self._W8_PROJS for n in names]
+            if _is_plain(*mods):
+                out.append((layer, mods))
+        return out
+
+    @property
+    def decode_weights(self) -> str:
+        """"bf16" or "e4m3": what set_decode_weights was last given."""
+        return self.__dict__.get("_decode_weights", "bf16")
+
+    def set_decode_weights(self, kind: str = "bf16"):
+        """How the decode step of generate() reads the decoder projections.
+
+        "bf16" (default): the weights as they are.  "e4m3": q|k|v, o, gate|up and down of every decoder layer are read as OCP e4m3 codes with one power-of-two
+        scale per output row (ops.gemv_w8: half the bytes of the bf16 weight stream); the codes are built from the current weights on first use and rebuilt after
+        an in-place update.  Only row blocks of at most 4 rows without autograd take that route: prefill, training, evaluate(), lm_head, the embeddings, the norms
+        and the vision tower are untouched, so prefill runs on the original bf16 weights and decode on their e4m3 rounding -- two slightly different functions
+        (about 2.6 % rel-L2 on the weights) unless snap_decoder_weights_to_e4m3_() has made the weights equal to their rounding.
+
+        Only layers whose projections are plain Linear modules are marked: a layer that still carries LoRA wrappers keeps the bf16 route.  Call
+        merge_and_unload() first, then set_decode_weights("e4m3"), to decode a fine-tuned model in e4m3."""
+        if kind not in ("bf16", "e4m3"):
+            raise ValueError(f"set_decode_weights: {kind!r} (\"bf16\" or \"e4m3\")")
+        for layer in self.model.layers:
+            layer.self_attn.__dict__.pop("_decode_w8", None)
+            layer.mlp.__dict__.pop("_decode_w8", None)
+        if kind == "e4m3":
+            for layer, mods in self._plain_decoder_projections():
+                if any(m.in_features % 16 for m in mods):
+                    raise ValueError("set_decode_weights(\"e4m3\"): every projection's input width must be a multiple of 16")
+                layer.self_attn.__dict__["_decode_w8"] = True
+                layer.mlp.__dict__["_decode_w8"] = True
+        self.__dict__["_decode_weights"] = kind
+        return self
+
+    @torch.no_grad()
+    def snap_decoder_weights_to_e4m3_(self):
+        """In place: W <- dequant(quant(W)) for the decoder projections set_decode_weights("e4m3") reads (the plain layers), so that prefill (bf16 kernels) and an
+        e4m3 decode step evaluate the same function.  Every snapped value is a bf16 number, so nothing else about the model changes; the original weights are
+        gone.  Idempotent in values: a second snap may pick another (code, scale) pair for a row whose largest element rounded down to a binade boundary, the
+        products are the same."""
+        for _, mods in self._plain_decoder_projections():
+            for m in mods:
+                w = m.weight
+                if w.dtype != torch.bfloat16 or not w.is_cuda or w.shape[1] % 16:
+                    raise ValueError("snap_decoder_weights_to_e4m3_: bf16 device weights with input widths that are multiples of 16")
+                w.copy_(ops.dequant_e4m3_rows(*ops.quant_e4m3_rows_pow2(w.detach())))
+        return self
+
     # -- generation (greedy / sampling) --------------------------------------------------------------------
     @torch.no_grad()
     def _capture_decode_step(self, cache, tok, pos_host):
@@ -957,7 +1043,8 @@ class Qwen2_5_VLForConditionalGeneration(nn.Module):
         dstate = None
         if graph_ok:
             cap = (S + max_new_tokens + 1023) // 1024 * 1024
-            dstate = self.__dict__.setdefault("_decode_states", {}).setdefault((cap, str(dev), self.dtype), {})
+            # (keyed by the decode-weight mode as well: a step captured on the bf16 stream is never replayed for e4m3 or the other way round)
+            dstate = self.__dict__.setdefault("_decode_states", {}).setdefault((cap, str(dev), self.dtype, self.decode_weights), {})
             # the captured launches read the weights (and the packs built from them) through their pointers: any in-place update since the
             # capture bumps a parameter version and the graph is dropped (re-captured on this call)
             sig = tuple((p.data_ptr(), p._version) for p in self.parameters())
