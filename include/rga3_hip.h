@@ -529,6 +529,23 @@ int rga3_quant_e4m3_rows_pow2(const void* w, void* q, float* scales, int64_t row
 int rga3_gemv_w8(const void* A, const void* Wq, const float* sw, const void* bias, const void* residual, void* C, int64_t M, int64_t N, int64_t K,
                  int64_t lda, int64_t ldw, int64_t ldc, int64_t ldr, int act, int out_dtype, void* stream);
 
+/* ---- Decode-step attention on the KV cache where it lies (csrc/decattn.hip): one call per decoder layer and decode step of generate() in place of
+ * rga3_rope_inplace + two rga3_scatter_rows + rga3_attn_varlen_fwd (HF modeling_qwen2_5_vl.py:602-757 with one query token per sequence).
+ * qkv [B, Hq + 2 Hkv, D] bf16: the fused, UN-rotated projection of the step (row stride ld_qkv, heads packed; read-only); cos / sin [B, D] f32 (contiguous);
+ * k_cache / v_cache [B, cap, Hkv, D] bf16 through (sequence, token, head) strides in elements, unit stride on D; lens [B] int32 ON THE DEVICE: the tokens already
+ * stored per sequence; out [B, Hq, D] bf16 (row stride ld_out, heads packed).  For every sequence b: the Hq query heads and the Hkv new key heads are rotated
+ * (rotate-half, rga3_rope_inplace's arithmetic: f32, one bf16 rounding), the rotated k row and the v row are stored at cache position lens[b], and
+ * out[b] = softmax(scale q K^T) V over cache rows 0 .. lens[b] inclusive; query head hq reads kv head hq / (Hq / Hkv).  Rows beyond lens[b] may hold anything.
+ * A sequence with lens[b] >= cap (or < 0) writes nothing to the caches and gets NaN output rows.  The keys of a sequence are cut into slices of
+ * rga3_decode_attn_slice_keys() keys by position alone, so a sequence's output bits do not depend on B, cap or the other sequences; no atomics, fixed order.
+ * Hq / Hkv <= 8; D % 16 == 0, D <= 128; strides multiples of 8; qkv and the caches 16-byte aligned; a sequence stride holds a whole [cap, Hkv, D] view.
+ * ws: rga3_decode_attn_ws_floats(B, cap, Hq, D) floats of caller workspace (< 0 = bad arguments), ws_floats its size; nothing in it needs zeroing. */
+int rga3_decode_attn_slice_keys(void);
+int64_t rga3_decode_attn_ws_floats(int64_t B, int64_t cap, int Hq, int D);
+int rga3_decode_attn(const void* qkv, const float* cos, const float* sin, void* k_cache, void* v_cache, const int32_t* lens, void* out, float* ws,
+                     int64_t ws_floats, int64_t B, int Hq, int Hkv, int D, int64_t cap, int64_t ld_qkv, int64_t k_sb, int64_t k_st, int64_t k_sh,
+                     int64_t v_sb, int64_t v_st, int64_t v_sh, int64_t ld_out, float scale, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1165,6 +1165,54 @@ def gemv_w8(a, wq, sw, bias=None, residual=None, act: str = "none", out_dtype=to
     return out
 
 
+_decattn_ws = {}
+
+
+def decode_attn_slice_keys() -> int:
+    """Keys per slice of decode_attn (a compile-time constant of csrc/decattn.hip): a sequence with n visible keys is cut into ceil(n / this) slices."""
+    return int(_lib.load().rga3_decode_attn_slice_keys())
+
+
+def decode_attn_ws_floats(B: int, cap: int, Hq: int, D: int) -> int:
+    n = int(_lib.load().rga3_decode_attn_ws_floats(B, cap, Hq, D))
+    if n < 0:
+        raise _lib.Rga3Error(f"decode_attn: bad workspace query (B={B} cap={cap} Hq={Hq} D={D})")
+    return n
+
+
+def decode_attn(qkv, cos, sin, k_cache, v_cache, lens, Hq: int, Hkv: int, scale: float, out=None, ws=None):
+    """One decode step's attention on the KV cache where it lies (rga3_decode_attn): qkv [B, Hq + 2 Hkv, D] bf16 is the fused UN-rotated projection (read-only),
+    cos / sin [B, D] f32, k_cache / v_cache [B, cap, Hkv, D] bf16 (any sequence / token / head strides, unit stride on D), lens [B] int32 on the device = tokens
+    already stored.  Rotates q and the new k, stores the rotated k row and the v row at position lens[b], returns softmax(scale q K^T) V over rows 0 .. lens[b]
+    as [B, Hq, D] bf16.  A sequence with lens[b] >= cap writes nothing and gets NaN rows.  ws: f32 workspace of decode_attn_ws_floats(B, cap, Hq, D) floats (kept per
+    device and stream / workspace_scope when not given)."""
+    if any(t is not None and not t.is_cuda for t in (qkv, cos, sin, k_cache, v_cache, lens, out, ws)):
+        raise _lib.Rga3Error("decode_attn: needs device tensors (no CPU fallback on the product path)")
+    assert qkv.dtype == k_cache.dtype == v_cache.dtype == torch.bfloat16 and qkv.dim() == 3 and k_cache.dim() == 4 and v_cache.dim() == 4
+    B, H, D = qkv.shape
+    assert H == Hq + 2 * Hkv and qkv.stride(2) == 1 and (qkv.stride(1) == D or H == 1), (qkv.shape, qkv.stride(), Hq, Hkv)
+    cap = k_cache.shape[1]
+    assert tuple(k_cache.shape) == (B, cap, Hkv, D) == tuple(v_cache.shape) and k_cache.stride(3) == 1 and v_cache.stride(3) == 1, (k_cache.shape, v_cache.shape)
+    assert cos.dtype == sin.dtype == torch.float32 and cos.is_contiguous() and sin.is_contiguous() and tuple(cos.shape) == (B, D) == tuple(sin.shape)
+    assert lens.dtype == torch.int32 and lens.numel() == B and lens.is_contiguous()
+    if out is None:
+        out = torch.empty((B, Hq, D), dtype=torch.bfloat16, device=qkv.device)
+    assert out.dtype == torch.bfloat16 and tuple(out.shape) == (B, Hq, D) and out.stride(2) == 1 and (out.stride(1) == D or Hq == 1)
+    L = _lib.load()
+    if ws is None:
+        n = decode_attn_ws_floats(B, cap, Hq, D)
+        key = _ws_key(qkv.device)
+        ws = _decattn_ws.get(key)
+        if ws is None or ws.numel() < n:
+            ws = _decattn_ws[key] = torch.empty(n, dtype=torch.float32, device=qkv.device)
+    assert ws.dtype == torch.float32 and ws.is_contiguous()
+    _lib.check(L.rga3_decode_attn(qkv.data_ptr(), cos.data_ptr(), sin.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), lens.data_ptr(), out.data_ptr(),
+                                  ws.data_ptr(), ws.numel(), B, Hq, Hkv, D, cap, qkv.stride(0),
+                                  k_cache.stride(0), k_cache.stride(1), k_cache.stride(2), v_cache.stride(0), v_cache.stride(1), v_cache.stride(2),
+                                  out.stride(0), float(scale), _stream()), "decode_attn")
+    return out
+
+
 def swiglu_fwd_quant(gu):
     """(e4m3 [T, I], scales [T]) of silu(gate) * up, as quant_fp8_rows(swiglu_fwd(gu)) gives them, without the bf16 tensor in between."""
     _need_cuda(gu)

@@ -512,6 +512,11 @@ class DecoderAttention(nn.Module):
             qkv = qkv_with_lora(self, h, seeds=getattr(self, "_lora_drop_seeds", None))[0].view(T, Hq + 2 * Hk, D)
         else:  # foreign wrappers (e.g. PEFT): honour them, then assemble the fused buffer
             qkv = torch.cat([self.q_proj(h), self.k_proj(h), self.v_proj(h)], dim=-1).view(T, Hq + 2 * Hk, D)
+        if (cache is not None and max_len == 1 and self.__dict__.get("_decode_attn_cache", False) and not torch.is_grad_enabled()
+                and qkv.dtype == torch.bfloat16 and cache.decode_ready(T)):
+            # set_decode_attention("cache"), decode step: rotation, the two cache appends and attention over the cache where it lies, in one call
+            att = cache.decode_attn(self.layer_idx, qkv, cos, sin, Hq, Hk, D ** -0.5)
+            return self._out_proj(att, T, residual, rms_out)
         q, k, v = qkv[:, :Hq], qkv[:, Hq:Hq + Hk], qkv[:, Hq + Hk:]
         # prefill without autograd: only the Hk key heads go through the stand-alone RoPE pass, the queries are rotated by the attention kernel as it loads them
         # (rga3_attn_varlen_fwd_rope -> attn_causal32_kernel: the rotate-half partner d + 64 sits in the same lane)
@@ -528,6 +533,10 @@ class DecoderAttention(nn.Module):
             att = ops.attn_varlen_rope(q, k, v, cu, cu_k, max_len, D ** -0.5, cos, sin, causal=True)
         else:
             att = ops.attn_varlen(q, k, v, cu, cu_k, max_len, D ** -0.5, causal=(max_len > 1))
+        return self._out_proj(att, T, residual, rms_out)
+
+    def _out_proj(self, att, T, residual, rms_out):
+        Hq, D = self.num_heads, self.head_dim
         if rms_out is not None:
             return ops.gemm(att.view(T, Hq * D), self.o_proj.weight, self.o_proj.bias, residual=residual, rms_out=rms_out)
         if _is_plain(self.o_proj) and _w8_ok(self, att):
@@ -566,6 +575,7 @@ class KVCache:
         self.cap = cap
         self._new = None
         self._cu = None
+        self._lens_dev = None
 
     def get_seq_length(self):
         return max(self.lens) if self.lens else 0
@@ -573,6 +583,18 @@ class KVCache:
     def begin(self, new_lens):
         self._new = list(new_lens)
         self._cu = None   # cu_k of this step: the same for every layer, built (one host -> device copy) by the first update()
+        self._lens_dev = None   # the stored lengths of this step on the device: the same for every layer, uploaded by the first decode_attn()
+
+    def decode_ready(self, T):
+        """This step appends exactly one token to every sequence (the shape ops.decode_attn serves)."""
+        return self._new is not None and len(self._new) == T and all(n == 1 for n in self._new)
+
+    def decode_attn(self, layer, qkv, cos, sin, Hq, Hk, scale):
+        """set_decode_attention("cache"): one decode step of `layer` for all sequences on the cache where it lies (no per-sequence copy, no concatenation); the
+        lengths go up once per step, without stalling the host."""
+        if self._lens_dev is None:
+            self._lens_dev = upload(np.asarray(self.lens, dtype=np.int32), qkv.device)
+        return ops.decode_attn(qkv, cos, sin, self.k[layer], self.v[layer], self._lens_dev, Hq, Hk, scale)
 
     def update(self, layer, k, v, cu_q):
         """Append this step's packed k/v and return packed (k_all, v_all, cu_k) views for attention."""
@@ -619,6 +641,9 @@ class StaticKVCache:
     def begin(self, new_lens):
         pass
 
+    def decode_ready(self, T):
+        return False      # this view serves the varlen route; set_decode_attention("cache") captures over StaticBatchKVCache
+
     def update(self, layer, k, v, cu_q):
         ops.scatter_rows_(self.k[layer][0].view(self.cap, -1), self.len_dev, k.reshape(1, -1))
         ops.scatter_rows_(self.v[layer][0].view(self.cap, -1), self.len_dev, v.reshape(1, -1))
@@ -630,6 +655,41 @@ class StaticKVCache:
     def advance(self):
         self.len_dev += 1
         self.cu_dev[1:] += 1
+
+
+class StaticBatchKVCache:
+    """Cache view of B sequences for the captured decode step under set_decode_attention("cache"): the [B, cap, Hkv, D] buffers of a KVCache with the stored
+    lengths ON THE DEVICE (lens_dev int32 [B]).  ops.decode_attn appends and attends at lens_dev, advance() moves it inside the graph, so one captured graph
+    serves every step of every batch of this size; one workspace is shared by all layers (they run one after the other)."""
+
+    def __init__(self, base: "KVCache", device):
+        self.k, self.v, self.cap = base.k, base.v, base.cap
+        self.batch = len(base.lens)
+        self.lens_dev = torch.tensor(base.lens, dtype=torch.int32, device=device)
+        self.ws = None
+
+    def reset(self, n_stored):
+        self.lens_dev.copy_(upload(np.asarray(n_stored, dtype=np.int32), self.lens_dev.device))
+
+    def begin(self, new_lens):
+        pass
+
+    def decode_ready(self, T):
+        return T == self.batch
+
+    def decode_attn(self, layer, qkv, cos, sin, Hq, Hk, scale):
+        if self.ws is None:
+            self.ws = torch.empty(ops.decode_attn_ws_floats(self.batch, self.cap, Hq, qkv.shape[2]), dtype=torch.float32, device=qkv.device)
+        return ops.decode_attn(qkv, cos, sin, self.k[layer], self.v[layer], self.lens_dev, Hq, Hk, scale, ws=self.ws)
+
+    def update(self, layer, k, v, cu_q):
+        raise RuntimeError("StaticBatchKVCache serves decode steps of set_decode_attention(\"cache\") only")
+
+    def commit(self):
+        pass
+
+    def advance(self):
+        self.lens_dev += 1
 
 
 class TextModel(nn.Module):
@@ -980,6 +1040,32 @@ class Qwen2_5_VLForConditionalGeneration(nn.Module):
         self.__dict__["_decode_weights"] = kind
         return self
 
+    @property
+    def decode_attention(self) -> str:
+        """"varlen" or "cache": what set_decode_attention was last given."""
+        return self.__dict__.get("_decode_attention", "varlen")
+
+    def set_decode_attention(self, kind: str = "varlen"):
+        """How a decode step (a cache present, one new token per sequence, no autograd) runs the attention third of a decoder layer.
+
+        "varlen" (default): RoPE in place, the new k / v rows appended to the cache, the packed variable-length attention kernel.  "cache": one ops.decode_attn call
+        that rotates q and k, appends k / v and attends over the [B, cap, Hkv, D] cache where it lies, with the lengths on the device -- no per-sequence copy and no
+        concatenation of the batch's caches, and generate() replays a captured step for 1 <= B <= 8 sequences instead of one.  Prefill, training and everything
+        under autograd are untouched; the q|k|v and o products around it follow set_decode_weights as before."""
+        if kind not in ("varlen", "cache"):
+            raise ValueError(f"set_decode_attention: {kind!r} (\"varlen\" or \"cache\")")
+        c = self.config
+        if kind == "cache":
+            G, D = c.num_attention_heads // c.num_key_value_heads, c.head_dim
+            if c.num_attention_heads % c.num_key_value_heads or G > 8 or D % 16 or D > 128:
+                raise ValueError(f"set_decode_attention(\"cache\"): {G} query heads per kv head (at most 8), head_dim {D} (a multiple of 16, at most 128)")
+        for layer in self.model.layers:
+            layer.self_attn.__dict__.pop("_decode_attn_cache", None)
+            if kind == "cache":
+                layer.self_attn.__dict__["_decode_attn_cache"] = True
+        self.__dict__["_decode_attention"] = kind
+        return self
+
     @torch.no_grad()
     def snap_decoder_weights_to_e4m3_(self):
         """In place: W <- dequant(quant(W)) for the decoder projections set_decode_weights("e4m3") reads (the plain layers), so that prefill (bf16 kernels) and an
@@ -997,13 +1083,17 @@ class Qwen2_5_VLForConditionalGeneration(nn.Module):
     # -- generation (greedy / sampling) --------------------------------------------------------------------
     @torch.no_grad()
     def _capture_decode_step(self, cache, tok, pos_host):
-        """First decode step of a single-sequence generate(): run it eagerly on a side stream (tuner picks, workspaces), then capture the same
-        step over static inputs (token id, position, device-side cache length).  Returns the replay state; its "logits" are those of the step
-        just taken.  The eager step and the captured one write the same cache row, so the cache is consistent whichever ran last."""
+        """First decode step of a generate() that replays a graph: run it eagerly on a side stream (tuner picks, workspaces), then capture the same
+        step over static inputs (token ids [B], positions [3, B], device-side cache lengths).  Returns the replay state; its "logits" are those of the step
+        just taken.  The eager step and the captured one write the same cache row, so the cache is consistent whichever ran last.
+        One sequence on the varlen route captures over StaticKVCache; set_decode_attention("cache") captures B sequences over StaticBatchKVCache."""
         dev = tok.device
-        n_stored = cache.lens[0]
-        st = {"tok": tok.clone(), "pos3": torch.from_numpy(np.broadcast_to(pos_host[None], (3, 1)).copy()).to(dev), "kv": StaticKVCache(cache, dev)}
-        st["cu_q"] = torch.tensor([0, 1], dtype=torch.int32, device=dev)   # every tensor the captured launches read must outlive the graph: keep it in st
+        B = tok.shape[0]
+        batched = self.decode_attention == "cache"
+        n_stored = list(cache.lens)
+        st = {"tok": tok.clone(), "pos3": torch.from_numpy(np.broadcast_to(pos_host[None], (3, B)).copy()).to(dev),
+              "kv": StaticBatchKVCache(cache, dev) if batched else StaticKVCache(cache, dev)}
+        st["cu_q"] = torch.arange(B + 1, dtype=torch.int32, device=dev)   # every tensor the captured launches read must outlive the graph: keep it in st
 
         def body():
             h, _ = self.model(ops.gather_rows(self.model.embed_tokens.weight, st["tok"]), st["pos3"], st["cu_q"], 1, st["kv"])
@@ -1019,12 +1109,12 @@ class Qwen2_5_VLForConditionalGeneration(nn.Module):
                 body()
             torch.cuda.current_stream().wait_stream(side)
             st["pos3"] -= 1                # rewind the state the warm-up advanced; the warm-up wrote cache row n_stored, the capture rewrites it
-            st["kv"].reset(n_stored)
+            st["kv"].reset(n_stored if batched else n_stored[0])
             st["graph"] = torch.cuda.CUDAGraph()
             with torch.cuda.graph(st["graph"]):
                 st["logits"] = body()
         st["graph"].replay()          # capturing executes nothing: the state still says "this step" -- now run it for real
-        cache.lens[0] = n_stored      # the host-side bookkeeping of the eager cache is not used any more during this call
+        cache.lens = n_stored         # the host-side bookkeeping of the eager cache is not used any more during this call
         return st
 
     def generate(self, input_ids=None, attention_mask=None, max_new_tokens=128, do_sample=False, temperature=1.0, top_p=1.0,
@@ -1038,13 +1128,14 @@ class Qwen2_5_VLForConditionalGeneration(nn.Module):
         eos = set(eos if isinstance(eos, (list, tuple)) else [eos])
         # single sequences decode by replaying a captured step: its KV buffers and graph are kept on the model per capacity bucket, so only the
         # first generate() of a given length class pays for the capture
-        graph_ok = (B == 1 and max_new_tokens >= 16 and not torch.is_grad_enabled() and kwargs.get("decode_graph", True)
+        attn_mode = self.decode_attention     # "cache": the captured step takes 1 <= B <= 8 sequences (ops.decode_attn reads the lengths on the device)
+        graph_ok = ((B == 1 or (attn_mode == "cache" and B <= 8)) and max_new_tokens >= 16 and not torch.is_grad_enabled() and kwargs.get("decode_graph", True)
                     and all(_is_plain(l.self_attn.q_proj, l.self_attn.k_proj, l.self_attn.v_proj) for l in self.model.layers))
         dstate = None
         if graph_ok:
             cap = (S + max_new_tokens + 1023) // 1024 * 1024
-            # (keyed by the decode-weight mode as well: a step captured on the bf16 stream is never replayed for e4m3 or the other way round)
-            dstate = self.__dict__.setdefault("_decode_states", {}).setdefault((cap, str(dev), self.dtype, self.decode_weights), {})
+            # (keyed by the batch size, the attention route and the decode-weight mode as well: a step captured for one of them is never replayed for another)
+            dstate = self.__dict__.setdefault("_decode_states", {}).setdefault((cap, str(dev), self.dtype, B, attn_mode, self.decode_weights), {})
             # the captured launches read the weights (and the packs built from them) through their pointers: any in-place update since the
             # capture bumps a parameter version and the graph is dropped (re-captured on this call)
             sig = tuple((p.data_ptr(), p._version) for p in self.parameters())
@@ -1052,9 +1143,9 @@ class Qwen2_5_VLForConditionalGeneration(nn.Module):
                 dstate.clear()
                 dstate["sig"] = sig
             if "cache" not in dstate:
-                dstate["cache"] = KVCache(c.num_hidden_layers, 1, cap, c.num_key_value_heads, c.head_dim, dev, self.dtype)
+                dstate["cache"] = KVCache(c.num_hidden_layers, B, cap, c.num_key_value_heads, c.head_dim, dev, self.dtype)
             cache = dstate["cache"]
-            cache.lens = [0]
+            cache.lens = [0] * B
         else:
             cache = KVCache(c.num_hidden_layers, B, S + max_new_tokens, c.num_key_value_heads, c.head_dim, dev, self.dtype)
         am = attention_mask if attention_mask is not None else torch.ones_like(input_ids)
@@ -1098,8 +1189,8 @@ class Qwen2_5_VLForConditionalGeneration(nn.Module):
                 # launch latency) is captured once (kept on the model per capacity bucket) after a first eager step and replayed per token
                 if dec is None and "graph" in dstate:          # captured by an earlier call: point the static state at this sequence
                     dec = dstate
-                    dec["pos3"].copy_(torch.from_numpy(np.broadcast_to(pos_host[None], (3, 1)).copy()).to(dev))
-                    dec["kv"].reset(cache.lens[0])
+                    dec["pos3"].copy_(torch.from_numpy(np.broadcast_to(pos_host[None], (3, B)).copy()).to(dev))
+                    dec["kv"].reset(cache.lens if attn_mode == "cache" else cache.lens[0])
                     dec["tok"].copy_(nxt)
                     dec["graph"].replay()
                 elif dec is None:
@@ -1111,7 +1202,10 @@ class Qwen2_5_VLForConditionalGeneration(nn.Module):
                     dec["graph"].replay()
                 logits = dec["logits"]
                 continue
-            pos3 = torch.from_numpy(np.broadcast_to(pos_host[None], (3, B)).copy()).to(dev)
+            if attn_mode == "cache":      # this route's step holds no host <-> device sync at all: the positions go up from pinned memory
+                pos3 = upload(np.broadcast_to(pos_host[None], (3, B)).copy(), dev)
+            else:
+                pos3 = torch.from_numpy(np.broadcast_to(pos_host[None], (3, B)).copy()).to(dev)
             cache.begin([1] * B)
             h, _ = self.model(ops.gather_rows(self.model.embed_tokens.weight, nxt), pos3, cu_dec, 1, cache)
             cache.commit()

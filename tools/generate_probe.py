@@ -1,22 +1,40 @@
 """Decode-step rate of generate() at 7B dims (random weights): prefill S = 2112 (16 frames), then N new tokens.
-python tools/generate_probe.py [N] [--decode-weights bf16|e4m3]"""
+python tools/generate_probe.py [N] [--decode-weights bf16|e4m3] [--decode-attn varlen|cache] [--batch B]
+--batch B repeats the bench sample B times along the batch; the third line's ms/token is per step (all B sequences), ms/token/seq divides it by B."""
 import os, sys, time, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "rga3-release_amd"))
 import bench
 args = sys.argv[1:]
-kind = "bf16"
-if "--decode-weights" in args:
-    i = args.index("--decode-weights")
-    kind = args[i + 1]
+
+
+def opt(name, default):
+    if name not in args:
+        return default
+    i = args.index(name)
+    v = args[i + 1]
     del args[i:i + 2]
+    return v
+
+
+kind = opt("--decode-weights", "bf16")
+attn = opt("--decode-attn", "varlen")
+B = int(opt("--batch", "1"))
 N = int(args[0]) if args else 64
 dev = torch.device("cuda:0")
 model, cfg = bench.build_model(dev)
 inputs = bench.make_inputs(cfg, dev)
+if B > 1:
+    inputs = dict(input_ids=inputs["input_ids"].repeat(B, 1), attention_mask=inputs["attention_mask"].repeat(B, 1),
+                  pixel_values_videos=inputs["pixel_values_videos"].repeat(B, 1), video_grid_thw=inputs["video_grid_thw"].repeat(B, 1),
+                  second_per_grid_ts=inputs["second_per_grid_ts"].repeat(B))
 if kind != "bf16":
     model.set_decode_weights(kind)
     print(f"decode weights: {model.decode_weights}", flush=True)
+if attn != "varlen":
+    model.set_decode_attention(attn)
+if attn != "varlen" or B > 1:
+    print(f"decode attention: {model.decode_attention}; batch {B}", flush=True)
 with torch.no_grad():
     for n in (8, N, N):
         torch.cuda.synchronize(); t0 = time.perf_counter()
@@ -24,4 +42,6 @@ with torch.no_grad():
         torch.cuda.synchronize(); t1 = time.perf_counter()
         out = model.generate(**inputs, max_new_tokens=n + 1, do_sample=False, eos_token_id=-1)    # (no EOS: random weights cannot end a run early)
         torch.cuda.synchronize(); t2 = time.perf_counter()
-        print(f"prefill+1: {(t1-t0)*1e3:.1f} ms; {n} more tokens: {((t2-t1)-(t1-t0))*1e3/n:.2f} ms/token; out {tuple(out.shape)}", flush=True)
+        per = ((t2 - t1) - (t1 - t0)) * 1e3 / n
+        print(f"prefill+1: {(t1-t0)*1e3:.1f} ms; {n} more tokens: {per:.2f} ms/token" + (f" ({per / B:.2f} ms/token/seq)" if B > 1 else "")
+              + f"; out {tuple(out.shape)}", flush=True)
