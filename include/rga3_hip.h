@@ -546,6 +546,30 @@ int rga3_decode_attn(const void* qkv, const float* cos, const float* sin, void* 
                      int64_t ws_floats, int64_t B, int Hq, int Hkv, int D, int64_t cap, int64_t ld_qkv, int64_t k_sb, int64_t k_st, int64_t k_sh,
                      int64_t v_sb, int64_t v_st, int64_t v_sh, int64_t ld_out, float scale, void* stream);
 
+/* ---- Next-token selection for generate() (csrc/select.hip): HF's RepetitionPenaltyLogitsProcessor -> TemperatureLogitsWarper -> TopKLogitsWarper ->
+ * TopPLogitsWarper and the draw (transformers generation/logits_process.py; reference app.py:308-317 through generation_config.json), per row in f32 with one
+ * IEEE operation per step (no contraction).  seen [B, V] uint8 with row stride ld_seen (bytes): non-zero = the token occurred in the prompt or was generated.
+ * rga3_mark_tokens: seen[b, ids[b, s]] = 1 for ids [B, S] int64 (row stride ld_ids); ids outside [0, V) are skipped; plain byte stores of one value, no atomics. */
+int rga3_mark_tokens(const int64_t* ids, void* seen, int64_t B, int64_t S, int64_t V, int64_t ld_ids, int64_t ld_seen, void* stream);
+/* out[b, v] (f32, row stride ld_out) = x where seen[b, v] == 0, else x < 0 ? x * penalty : x / penalty, x = logits[b, v] (dtype RGA3_BF16 or RGA3_F32, row stride
+ * ld_logits) as f32.  penalty > 0. */
+int rga3_penalize_logits(const void* logits, int dtype, const void* seen, float* out, int64_t B, int64_t V, int64_t ld_logits, int64_t ld_seen, int64_t ld_out,
+                         float penalty, void* stream);
+/* One token per row, two launches (vocabulary slices x B blocks that leave each slice's best top_k candidates, then one block per row that merges them):
+ *   1. s = logits[b, v] as f32; penalised as above where seen (seen may be null: no penalty); s = s / temperature.
+ *   2. candidates in the order (s descending, index ascending), -0.0 == +0.0; the first K = min(top_k, V).
+ *   3. w_j = exp(s_j - s_0), Z = sum of w_j in candidate order.
+ *   4. candidate j is kept iff j == 0 or sum_{i >= j} w_i (summed from the last candidate upwards) > (1 - top_p) * Z: a prefix of n candidates (HF's top-p rule).
+ *   5. u null: candidate 0.  Else with Z_n = sum_{i < n} w_i: the first kept j with sum_{i <= j} w_i > u[b] * Z_n, the last kept if there is none.
+ *   6. tok_out[b] = its index; seen[b, index] = 1 when seen is given (a plain byte store by the same thread).
+ * Deterministic (no atomics; the result does not depend on how the vocabulary is sliced).  -inf logits are legal; with NaN logits only 0 <= tok_out[b] < V holds.
+ * At an exact tie across the k-th place HF keeps every tied token, this keeps the lower indices.  temperature > 0, 1 <= top_k <= 64, 0 < top_p <= 1, penalty > 0,
+ * 1 <= B <= 65535, 1 <= V <= 2^31; u [B] f32 in [0, 1) or null; tok_out [B] int64; ws: rga3_select_ws_bytes(B, V) bytes (< 0 = bad shape), 8-byte aligned,
+ * nothing in it needs zeroing. */
+int64_t rga3_select_ws_bytes(int64_t B, int64_t V);
+int rga3_select_token(const void* logits, int dtype, void* seen, float penalty, float temperature, int top_k, float top_p, const float* u, int64_t* tok_out,
+                      void* ws, int64_t ws_bytes, int64_t B, int64_t V, int64_t ld_logits, int64_t ld_seen, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -91,6 +91,10 @@ SIGNATURES = {
     "rga3_decode_attn_slice_keys": [],
     "rga3_decode_attn_ws_floats": [_i64, _i64, _i, _i],
     "rga3_decode_attn": [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i, _i, _i, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f, _p],
+    "rga3_mark_tokens": [_p, _p, _i64, _i64, _i64, _i64, _i64, _p],
+    "rga3_penalize_logits": [_p, _i, _p, _p, _i64, _i64, _i64, _i64, _i64, _f, _p],
+    "rga3_select_ws_bytes": [_i64, _i64],
+    "rga3_select_token": [_p, _i, _p, _f, _f, _i, _f, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _p],
     "rga3_im2col3x3s2": [_p, _p, _i64, _i, _i, _i, _p],
     "rga3_pil_bicubic_coeffs": [_i, _i, _p, _p, _i64, _p],
     "rga3_sam_preprocess_u8": [_p, _i64, _i, _i, _i, _i, _p, _p, _i, _p, _p, _i, _p, _p, _p, _p, _p, _p],
@@ -124,7 +128,7 @@ SIGNATURES = {
     "rga3_bce_dice_grad_dev": [_p, _p, _p, _p, _i64, _i64, _p, _p, _p],
 }
 
-_INT64_RESULTS = ("rga3_gemm_lnsum_slices", "rga3_hiera_mlp288_pack_bytes", "rga3_gemm_workspace_bytes", "rga3_memattn_cross_ws_floats", "rga3_gemm_timeout_counter_offset", "rga3_layernorm_bwd_ws_floats", "rga3_colsum_ws_floats", "rga3_mask_product_bwd_ws_floats", "rga3_bce_dice_sums_ws_floats", "rga3_mask_jf_ws_bytes", "rga3_stom_ws_bytes", "rga3_decode_attn_ws_floats")
+_INT64_RESULTS = ("rga3_gemm_lnsum_slices", "rga3_hiera_mlp288_pack_bytes", "rga3_gemm_workspace_bytes", "rga3_memattn_cross_ws_floats", "rga3_gemm_timeout_counter_offset", "rga3_layernorm_bwd_ws_floats", "rga3_colsum_ws_floats", "rga3_mask_product_bwd_ws_floats", "rga3_bce_dice_sums_ws_floats", "rga3_mask_jf_ws_bytes", "rga3_stom_ws_bytes", "rga3_decode_attn_ws_floats", "rga3_select_ws_bytes")
 
 _lib = None
 

@@ -1213,6 +1213,94 @@ def decode_attn(qkv, cos, sin, k_cache, v_cache, lens, Hq: int, Hkv: int, scale:
     return out
 
 
+SELECT_MAX_TOP_K = 64     # rga3_select_token's candidate limit (csrc/select.hip kMaxTopK)
+
+
+def _select_refuse(cond, msg):
+    if not cond:
+        raise _lib.Rga3Error("select: " + msg)
+
+
+def _select_logits(logits, who):
+    _select_refuse(logits.is_cuda, f"{who} needs device tensors (no CPU fallback on the product path)")
+    _select_refuse(logits.dtype in (torch.bfloat16, torch.float32), f"{who}: logits must be bf16 or f32, not {logits.dtype}")
+    _select_refuse(logits.dim() == 2 and logits.shape[0] >= 1 and logits.shape[1] >= 1 and logits.stride(1) == 1, f"{who}: logits must be [B, V] with unit column stride")
+    B, V = logits.shape
+    _select_refuse(B == 1 or logits.stride(0) >= V, f"{who}: logits row stride {logits.stride(0)} is shorter than V = {V}")
+    return B, V
+
+
+def _select_seen(seen, B, V, who):
+    _select_refuse(seen.is_cuda, f"{who} needs device tensors (no CPU fallback on the product path)")
+    _select_refuse(seen.dtype == torch.uint8, f"{who}: seen must be uint8, not {seen.dtype}")
+    _select_refuse(seen.dim() == 2 and tuple(seen.shape) == (B, V) and seen.stride(1) == 1, f"{who}: seen must be [{B}, {V}] with unit column stride, not {tuple(seen.shape)}")
+    _select_refuse(B == 1 or seen.stride(0) >= V, f"{who}: seen row stride {seen.stride(0)} is shorter than V = {V}")
+
+
+def mark_tokens_(seen, ids):
+    """seen[b, ids[b, s]] = 1 in place (rga3_mark_tokens): seen [B, V] uint8 (row stride free), ids [B, S] int64; ids outside [0, V) are skipped.  What HF's
+    RepetitionPenaltyLogitsProcessor gathers: every id of the prompt, padding and vision placeholders included."""
+    _select_refuse(seen.is_cuda and ids.is_cuda, "mark_tokens_ needs device tensors (no CPU fallback on the product path)")
+    _select_refuse(ids.dtype == torch.int64, f"mark_tokens_: ids must be int64, not {ids.dtype}")
+    _select_refuse(ids.dim() == 2 and (ids.shape[1] == 0 or ids.stride(1) == 1), "mark_tokens_: ids must be [B, S] with unit column stride")
+    B, S = ids.shape
+    _select_refuse(seen.dim() == 2 and seen.shape[0] == B, f"mark_tokens_: seen {tuple(seen.shape)} does not match ids {tuple(ids.shape)}")
+    _select_seen(seen, B, seen.shape[1], "mark_tokens_")
+    _select_refuse(B == 1 or S == 0 or ids.stride(0) >= S, f"mark_tokens_: ids row stride {ids.stride(0)} is shorter than S = {S}")
+    _lib.check(_lib.load().rga3_mark_tokens(ids.data_ptr(), seen.data_ptr(), B, S, seen.shape[1], ids.stride(0), seen.stride(0), _stream()), "mark_tokens")
+    return seen
+
+
+def penalize_logits(logits, seen, penalty: float, out=None):
+    """f32 [B, V]: x where seen == 0, else x < 0 ? x * penalty : x / penalty (rga3_penalize_logits; HF RepetitionPenaltyLogitsProcessor).  logits bf16 or f32."""
+    B, V = _select_logits(logits, "penalize_logits")
+    _select_seen(seen, B, V, "penalize_logits")
+    _select_refuse(float(penalty) > 0, f"penalize_logits: penalty {penalty} must be positive")
+    if out is None:
+        out = torch.empty((B, V), dtype=torch.float32, device=logits.device)
+    _select_refuse(out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (B, V) and out.stride(1) == 1 and (B == 1 or out.stride(0) >= V),
+                   f"penalize_logits: out must be a device f32 [{B}, {V}] view whose rows hold V elements")
+    _lib.check(_lib.load().rga3_penalize_logits(logits.data_ptr(), BF16 if logits.dtype == torch.bfloat16 else F32, seen.data_ptr(), out.data_ptr(), B, V,
+                                                logits.stride(0), seen.stride(0), out.stride(0), float(penalty), _stream()), "penalize_logits")
+    return out
+
+
+def select_ws_bytes(B: int, V: int) -> int:
+    """Bytes of scratch select_token needs for [B, V] logits (rga3_select_ws_bytes)."""
+    n = int(_lib.load().rga3_select_ws_bytes(B, V))
+    if n < 0:
+        raise _lib.Rga3Error(f"select: bad workspace query (B={B} V={V})")
+    return n
+
+
+def select_token(logits, seen=None, penalty: float = 1.0, temperature: float = 1.0, top_k: int = 1, top_p: float = 1.0, u=None, out=None, ws=None):
+    """The next token of every row (rga3_select_token, two launches, no sync): repetition penalty on the tokens marked in seen, / temperature, the best top_k
+    candidates by (score descending, index ascending), HF's top-p cut, then candidate 0 (u None: greedy) or the draw u [B] f32 in [0, 1) over the kept candidates.
+    logits [B, V] bf16 or f32 (row stride free); seen [B, V] uint8 or None, updated in place with the chosen tokens; out [B] int64; ws: uint8 scratch of
+    select_ws_bytes(B, V) bytes (allocated when not given).  Returns out."""
+    B, V = _select_logits(logits, "select_token")
+    if seen is not None:
+        _select_seen(seen, B, V, "select_token")
+    _select_refuse(float(penalty) > 0, f"select_token: penalty {penalty} must be positive")
+    _select_refuse(float(temperature) > 0, f"select_token: temperature {temperature} must be positive")
+    _select_refuse(isinstance(top_k, int) and 1 <= top_k <= SELECT_MAX_TOP_K, f"select_token: top_k {top_k} outside 1..{SELECT_MAX_TOP_K}")
+    _select_refuse(0 < float(top_p) <= 1, f"select_token: top_p {top_p} outside (0, 1]")
+    if u is not None:
+        _select_refuse(u.is_cuda and u.dtype == torch.float32 and tuple(u.shape) == (B,) and u.is_contiguous(), f"select_token: u must be a contiguous device f32 [{B}]")
+    if out is None:
+        out = torch.empty((B,), dtype=torch.int64, device=logits.device)
+    _select_refuse(out.is_cuda and out.dtype == torch.int64 and tuple(out.shape) == (B,) and out.is_contiguous(), f"select_token: out must be a contiguous device int64 [{B}]")
+    need = select_ws_bytes(B, V)
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=logits.device)
+    _select_refuse(ws.is_cuda and ws.dtype == torch.uint8 and ws.dim() == 1 and ws.is_contiguous(), "select_token: ws must be a contiguous device uint8 vector")
+    _select_refuse(ws.numel() >= need, f"select_token: ws holds {ws.numel()} bytes, {need} needed (select_ws_bytes)")
+    _lib.check(_lib.load().rga3_select_token(logits.data_ptr(), BF16 if logits.dtype == torch.bfloat16 else F32, _ptr(seen), float(penalty), float(temperature),
+                                             int(top_k), float(top_p), _ptr(u), out.data_ptr(), ws.data_ptr(), ws.numel(), B, V, logits.stride(0),
+                                             seen.stride(0) if seen is not None else 0, _stream()), "select_token")
+    return out
+
+
 def swiglu_fwd_quant(gu):
     """(e4m3 [T, I], scales [T]) of silu(gate) * up, as quant_fp8_rows(swiglu_fwd(gu)) gives them, without the bf16 tensor in between."""
     _need_cuda(gu)

@@ -135,6 +135,96 @@ def _jsonable(v):
         return False
 
 
+_NOT_PASSED = type("_NotPassed", (), {"__repr__": lambda self: "<not passed>"})()   # generate(): "the caller did not give this argument"
+
+
+class GenerationConfig:
+    """The part of a checkpoint's generation_config.json that generate() honours, as plain attributes (HF GenerationConfig's names).  None switches a processor
+    off; keys this class does not know are kept and written back unchanged."""
+    FIELDS = ("do_sample", "temperature", "top_k", "top_p", "repetition_penalty", "eos_token_id", "pad_token_id", "max_new_tokens")
+    FILE = "generation_config.json"
+
+    def __init__(self, do_sample=False, temperature=None, top_k=None, top_p=None, repetition_penalty=None, eos_token_id=None, pad_token_id=None,
+                 max_new_tokens=None, **extra):
+        self.do_sample, self.temperature, self.top_k, self.top_p = bool(do_sample), temperature, top_k, top_p
+        self.repetition_penalty, self.eos_token_id, self.pad_token_id, self.max_new_tokens = repetition_penalty, eos_token_id, pad_token_id, max_new_tokens
+        self.extra = extra
+
+    def to_dict(self):
+        d = {k: getattr(self, k) for k in self.FIELDS if getattr(self, k) is not None}
+        d.update({k: v for k, v in self.extra.items() if _jsonable(v)})
+        return d
+
+    @classmethod
+    def from_dict(cls, d):
+        return cls(**d)
+
+    @classmethod
+    def from_pretrained(cls, path):
+        """<path>/generation_config.json, or None when the checkpoint has none."""
+        f = os.path.join(path, cls.FILE)
+        if not os.path.exists(f):
+            return None
+        with open(f) as fh:
+            return cls.from_dict(json.load(fh))
+
+    def save_pretrained(self, path):
+        os.makedirs(path, exist_ok=True)
+        with open(os.path.join(path, self.FILE), "w") as f:
+            json.dump(self.to_dict(), f, indent=2)
+
+    def __eq__(self, other):
+        return isinstance(other, GenerationConfig) and self.to_dict() == other.to_dict()
+
+    def __repr__(self):
+        return f"GenerationConfig({self.to_dict()})"
+
+
+def resolve_generation(generation_config, config, max_new_tokens=_NOT_PASSED, do_sample=_NOT_PASSED, temperature=_NOT_PASSED, top_k=_NOT_PASSED, top_p=_NOT_PASSED,
+                       repetition_penalty=_NOT_PASSED, eos_token_id=_NOT_PASSED):
+    """What one generate() call runs with, after HF's generation_config.update(**kwargs): an argument that was not passed takes the generation config's value, or the
+    built-in default when there is none (greedy, temperature 1, no top-k, top_p 1, penalty 1, 128 new tokens); None switches that processor off; any other value wins.
+    eos: argument, then generation config, then the model config; pad: generation config, then model config (None: generate() pads with an eos id).  Returns a dict with `route`:
+    "default" (argmax, or softmax + multinomial), "select" (ops.select_token) or "penalize" (ops.penalize_logits, then softmax + multinomial)."""
+    gc = generation_config
+    SELECT_MAX_TOP_K = ops.SELECT_MAX_TOP_K
+
+    def pick(arg, name, off):
+        v = arg if arg is not _NOT_PASSED else (getattr(gc, name) if gc is not None else off)
+        return off if v is None else v
+
+    r = {"max_new_tokens": int(pick(max_new_tokens, "max_new_tokens", 128)), "do_sample": bool(pick(do_sample, "do_sample", False)),
+         "temperature": float(pick(temperature, "temperature", 1.0)), "top_k": int(pick(top_k, "top_k", 0)), "top_p": float(pick(top_p, "top_p", 1.0)),
+         "repetition_penalty": float(pick(repetition_penalty, "repetition_penalty", 1.0))}
+    eos = eos_token_id if eos_token_id is not _NOT_PASSED and eos_token_id is not None else None
+    if eos is None and gc is not None:
+        eos = gc.eos_token_id
+    if eos is None:
+        eos = config.eos_token_id
+    r["eos_token_id"] = sorted(set(eos if isinstance(eos, (list, tuple)) else [eos]))
+    r["pad_token_id"] = gc.pad_token_id if gc is not None and gc.pad_token_id is not None else config.pad_token_id
+    if r["repetition_penalty"] <= 0:
+        raise ValueError(f"generate: repetition_penalty {r['repetition_penalty']} must be positive")
+    if not 0 < r["top_p"] <= 1:
+        raise ValueError(f"generate: top_p {r['top_p']} outside (0, 1]")
+    if r["top_k"] < 0:
+        raise ValueError(f"generate: top_k {r['top_k']} is negative")
+    pen = r["repetition_penalty"] != 1.0
+    if not r["do_sample"]:      # greedy: the warpers (temperature, top-k, top-p) do not apply, the penalty does (HF applies it in greedy search too)
+        r["route"] = "select" if pen else "default"
+    elif r["top_k"] > SELECT_MAX_TOP_K:
+        raise NotImplementedError(f"generate: sampling with top_k = {r['top_k']}: the selector holds at most {SELECT_MAX_TOP_K} candidates")
+    elif r["top_k"] >= 1:
+        if r["temperature"] <= 0:
+            raise ValueError(f"generate: temperature {r['temperature']} must be positive")
+        r["route"] = "select"
+    elif r["top_p"] < 1:
+        raise NotImplementedError(f"generate: sampling with top_p = {r['top_p']} needs a top_k of 1..{SELECT_MAX_TOP_K}: nucleus sampling over the whole vocabulary is not implemented")
+    else:
+        r["route"] = "penalize" if pen else "default"
+    return r
+
+
 @dataclass
 class CausalLMOutput:
     loss: Optional[torch.Tensor] = None
@@ -748,6 +838,7 @@ class Qwen2_5_VLForConditionalGeneration(nn.Module):
             self.lm_head.weight = self.model.embed_tokens.weight
         self.rope_deltas = None
         self.gradient_checkpointing = False
+        self.generation_config = None     # a GenerationConfig when the checkpoint carried generation_config.json (from_pretrained), or set by the caller
 
     # -- HF surface used by the reference's callers --------------------------------------
     @property
@@ -1117,15 +1208,26 @@ class Qwen2_5_VLForConditionalGeneration(nn.Module):
         cache.lens = n_stored         # the host-side bookkeeping of the eager cache is not used any more during this call
         return st
 
-    def generate(self, input_ids=None, attention_mask=None, max_new_tokens=128, do_sample=False, temperature=1.0, top_p=1.0,
-                 eos_token_id=None, pixel_values=None, pixel_values_videos=None, image_grid_thw=None, video_grid_thw=None,
-                 second_per_grid_ts=None, **kwargs):
-        """Prefill + KV-cached decode; returns [B, S + new] token ids (reference app.py:308-317 usage)."""
+    def generate(self, input_ids=None, attention_mask=None, max_new_tokens=_NOT_PASSED, do_sample=_NOT_PASSED, temperature=_NOT_PASSED, top_p=_NOT_PASSED,
+                 eos_token_id=_NOT_PASSED, pixel_values=None, pixel_values_videos=None, image_grid_thw=None, video_grid_thw=None,
+                 second_per_grid_ts=None, top_k=_NOT_PASSED, repetition_penalty=_NOT_PASSED, generation_config=None, seed=None, **kwargs):
+        """Prefill + KV-cached decode; returns [B, S + new] token ids (reference app.py:308-317 usage).
+
+        The sampling arguments resolve as HF's do (resolve_generation): not passed = the value of `generation_config` (else of self.generation_config, read from
+        the checkpoint's generation_config.json), or the built-in default when the model has none (128 new tokens, greedy, temperature 1, no top-k, top_p 1,
+        penalty 1, eos of the model config); None = that processor off.  A repetition penalty != 1, or sampling with 1 <= top_k <= 64, picks the token with
+        ops.select_token (HF's processors in f32: penalty over every id of input_ids and every generated id, temperature, top-k, top-p, then the draw from
+        u = torch.rand(B) of a generator seeded with `seed`, the default generator when seed is None); a penalty with plain sampling goes through
+        ops.penalize_logits; everything else is argmax or softmax + multinomial as before.  Sampling with top_p < 1 and no top-k, or top_k > 64, raises."""
         c = self.config
         B, S = input_ids.shape
         dev = self.device
-        eos = eos_token_id if eos_token_id is not None else c.eos_token_id
-        eos = set(eos if isinstance(eos, (list, tuple)) else [eos])
+        gen = resolve_generation(generation_config if generation_config is not None else self.generation_config, c, max_new_tokens=max_new_tokens,
+                                 do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty,
+                                 eos_token_id=eos_token_id)
+        max_new_tokens, do_sample, temperature, route = gen["max_new_tokens"], gen["do_sample"], gen["temperature"], gen["route"]
+        eos = set(gen["eos_token_id"])
+        rng = torch.Generator(device=dev).manual_seed(int(seed)) if seed is not None else None
         # single sequences decode by replaying a captured step: its KV buffers and graph are kept on the model per capacity bucket, so only the
         # first generate() of a given length class pays for the capture
         attn_mode = self.decode_attention     # "cache": the captured step takes 1 <= B <= 8 sequences (ops.decode_attn reads the lengths on the device)
@@ -1156,7 +1258,13 @@ class Qwen2_5_VLForConditionalGeneration(nn.Module):
         logits = out.logits[torch.arange(B, device=dev), last_idx.to(dev)]
         seqs = input_ids
         done = torch.zeros(B, dtype=torch.bool, device=dev)
-        pad = c.pad_token_id if c.pad_token_id is not None else next(iter(eos))
+        pad = gen["pad_token_id"] if gen["pad_token_id"] is not None else next(iter(eos))
+        seen = sel_ws = None
+        if route != "default":     # the penalty's state: one byte per (sequence, token), set for every id of the prompt (padding and vision placeholders too, as HF gathers them)
+            V = logits.shape[-1]
+            seen = ops.mark_tokens_(torch.zeros((B, V), dtype=torch.uint8, device=dev), input_ids.to(dev))
+            if route == "select":
+                sel_ws = torch.empty(ops.select_ws_bytes(B, V), dtype=torch.uint8, device=dev)
         eos_t = torch.tensor(sorted(eos), device=dev)
         new_cols, all_done = [], []
         deltas = self.rope_deltas.cpu().numpy().reshape(B) if self.rope_deltas is not None else np.zeros(B, dtype=np.int64)
@@ -1168,9 +1276,19 @@ class Qwen2_5_VLForConditionalGeneration(nn.Module):
         # columns (all pad by construction) are cut below, so the returned ids are exactly those of the step-by-step loop.
         SYNC_EVERY = 8
         for step in range(max_new_tokens):
-            if do_sample:
+            if route == "select":      # two eager launches between the graph replays, no sync; the kernel also marks the token it picked in `seen`
+                if do_sample:
+                    nxt = ops.select_token(logits, seen, gen["repetition_penalty"], temperature, gen["top_k"], gen["top_p"],
+                                           torch.rand(B, device=dev, generator=rng), ws=sel_ws)
+                else:
+                    nxt = ops.select_token(logits, seen, gen["repetition_penalty"], ws=sel_ws)
+            elif route == "penalize":
+                pr = torch.softmax(ops.penalize_logits(logits, seen, gen["repetition_penalty"]) / max(temperature, 1e-5), -1)
+                nxt = torch.multinomial(pr, 1, generator=rng)[:, 0]
+                ops.mark_tokens_(seen, nxt[:, None])
+            elif do_sample:
                 pr = torch.softmax(logits.float() / max(temperature, 1e-5), -1)
-                nxt = torch.multinomial(pr, 1)[:, 0]
+                nxt = torch.multinomial(pr, 1, generator=rng)[:, 0]
             else:
                 nxt = logits.float().argmax(-1)
             nxt = torch.where(done, torch.full_like(nxt, pad), nxt)

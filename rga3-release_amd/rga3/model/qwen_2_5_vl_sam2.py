@@ -20,7 +20,7 @@ import torch.nn as nn
 from ..hip import autograd as AG
 from ..hip import ops
 from ..utils.staging import host_of, upload
-from .qwen2_5_vl import CausalLMOutput, Linear, Qwen2_5_VLConfig, Qwen2_5_VLForConditionalGeneration
+from .qwen2_5_vl import CausalLMOutput, GenerationConfig, Linear, Qwen2_5_VLConfig, Qwen2_5_VLForConditionalGeneration
 from .sam2 import SAM2
 
 
@@ -91,6 +91,7 @@ class UniGRModel(Qwen2_5_VLForConditionalGeneration):
         finally:
             torch.set_default_dtype(old)
         CK.load_checkpoint(model, path, strict=strict)
+        model.generation_config = GenerationConfig.from_pretrained(path)     # None when the checkpoint has no generation_config.json
         return model
 
     def save_pretrained(self, path, state_dict=None, max_shard_size=5 * 2**30, **unused):
@@ -98,6 +99,8 @@ class UniGRModel(Qwen2_5_VLForConditionalGeneration):
         from ..utils import checkpoint as CK
 
         CK.save_checkpoint(state_dict if state_dict is not None else self, path, max_shard_bytes=max_shard_size, config=self.config)
+        if self.generation_config is not None:
+            self.generation_config.save_pretrained(path)
 
     def merge_and_unload(self):
         """PEFT's call on the wrapped model (merge_lora_weights_and_save_hf_model.py:133): fold the LoRA factors into q_proj / v_proj."""

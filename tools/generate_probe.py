@@ -1,6 +1,8 @@
 """Decode-step rate of generate() at 7B dims (random weights): prefill S = 2112 (16 frames), then N new tokens.
-python tools/generate_probe.py [N] [--decode-weights bf16|e4m3] [--decode-attn varlen|cache] [--batch B]
---batch B repeats the bench sample B times along the batch; the third line's ms/token is per step (all B sequences), ms/token/seq divides it by B."""
+python tools/generate_probe.py [N] [--decode-weights bf16|e4m3] [--decode-attn varlen|cache] [--batch B] [--repetition-penalty P] [--top-k K] [--top-p P] [--sample]
+--batch B repeats the bench sample B times along the batch; the third line's ms/token is per step (all B sequences), ms/token/seq divides it by B.
+--repetition-penalty / --top-k / --top-p / --sample go to generate() as given (a penalty != 1, or --sample with a top-k, picks tokens with ops.select_token; --sample draws
+with seed 0); without them the call is the plain greedy one."""
 import os, sys, time, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "rga3-release_amd"))
@@ -20,6 +22,15 @@ def opt(name, default):
 kind = opt("--decode-weights", "bf16")
 attn = opt("--decode-attn", "varlen")
 B = int(opt("--batch", "1"))
+sel = {}
+for name, key, conv in (("--repetition-penalty", "repetition_penalty", float), ("--top-k", "top_k", int), ("--top-p", "top_p", float)):
+    v = opt(name, None)
+    if v is not None:
+        sel[key] = conv(v)
+if "--sample" in args:
+    args.remove("--sample")
+    sel.update(do_sample=True, seed=0)
+sel.setdefault("do_sample", False)
 N = int(args[0]) if args else 64
 dev = torch.device("cuda:0")
 model, cfg = bench.build_model(dev)
@@ -35,12 +46,14 @@ if attn != "varlen":
     model.set_decode_attention(attn)
 if attn != "varlen" or B > 1:
     print(f"decode attention: {model.decode_attention}; batch {B}", flush=True)
+if len(sel) > 1:
+    print("token selection: " + ", ".join(f"{k}={v}" for k, v in sorted(sel.items())), flush=True)
 with torch.no_grad():
     for n in (8, N, N):
         torch.cuda.synchronize(); t0 = time.perf_counter()
-        out = model.generate(**inputs, max_new_tokens=1, do_sample=False, eos_token_id=-1)
+        out = model.generate(**inputs, max_new_tokens=1, eos_token_id=-1, **sel)
         torch.cuda.synchronize(); t1 = time.perf_counter()
-        out = model.generate(**inputs, max_new_tokens=n + 1, do_sample=False, eos_token_id=-1)    # (no EOS: random weights cannot end a run early)
+        out = model.generate(**inputs, max_new_tokens=n + 1, eos_token_id=-1, **sel)    # (no EOS: random weights cannot end a run early)
         torch.cuda.synchronize(); t2 = time.perf_counter()
         per = ((t2 - t1) - (t1 - t0)) * 1e3 / n
         print(f"prefill+1: {(t1-t0)*1e3:.1f} ms; {n} more tokens: {per:.2f} ms/token" + (f" ({per / B:.2f} ms/token/seq)" if B > 1 else "")
