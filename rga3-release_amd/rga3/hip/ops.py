@@ -11,7 +11,9 @@ import torch
 
 from . import lib as _lib
 from . import tuner as _tuner
+from . import scratch as _scratch
 from .derived import derived as _derived
+from .scratch import Scratch, capture_step, drop_if_weights_changed, workspace_scope  # noqa: F401  (callers say ops.workspace_scope, ops.capture_step, ...)
 
 BF16, F32 = 0, 1
 ACT = {"none": 0, "gelu": 1, "swiglu": 2, "relu": 3}
@@ -41,54 +43,25 @@ def pad_cols(x: torch.Tensor, ld: int) -> torch.Tensor:
     return out
 
 
-_gemm_ws = {}
-_ws_scope = [None]
-
-
-class workspace_scope:
-    """``with ops.workspace_scope(token): ...`` -- every scratch buffer this module hands to a kernel (stream-K slabs / flags, the memory cross-attention's partial
-    sums, the TN ticket words) is keyed by (device, token) instead of (device, current stream) inside the block.  A captured hipGraph bakes the POINTERS it saw, and a
-    graph is replayed on whatever stream is current -- so the scratch of a capture must belong to the graph's owner, not to a stream handle: torch.cuda.Stream() hands
-    out streams of a pool of 32 round-robin, and a later eager launch on a stream that happens to BE some capture stream would share that graph's scratch while the
-    graph replays elsewhere (round 6: an intermittent mismatch of the concurrent object slots at the configs[3] shape).  The owner replays its graphs one after the
-    other; warm-up and capture both run inside the scope so that every buffer exists before the capture."""
-
-    def __init__(self, token):
-        self.token = ("scope", token)
-
-    def __enter__(self):
-        self.old, _ws_scope[0] = _ws_scope[0], self.token
-        return self
-
-    def __exit__(self, *exc):
-        _ws_scope[0] = self.old
-
-
-def _ws_key(device):
-    dev = device.index if device.index is not None else torch.cuda.current_device()
-    return (dev, _ws_scope[0] if _ws_scope[0] is not None else torch.cuda.current_stream(device).cuda_stream)
-
-
 def gemm_workspace(device) -> torch.Tensor:
-    """The caller-owned workspace of the stream-K / split-K GEMM tilings for (device, current stream) -- or (device, workspace_scope token): allocated from PyTorch's
-    caching allocator on first use, zeroed once (the flag words; the kernels leave them zero), then kept for the life of the process."""
-    key = _ws_key(device)
-    t = _gemm_ws.get(key)
+    """The caller-owned workspace of the stream-K / split-K GEMM tilings of the current Scratch (scratch.of: the workspace_scope's, else that of (device, current
+    stream)): allocated from PyTorch's caching allocator on first use, zeroed once (the flag words; the kernels leave them zero), then kept as long as its Scratch."""
+    t = _scratch.of(device).gemm
     if t is None:
         with torch.cuda.device(device):
             n = int(_lib.load().rga3_gemm_workspace_bytes())
         if n <= 0:
             raise _lib.Rga3Error("rga3_gemm_workspace_bytes failed: " + _lib.last_error())
-        t = _gemm_ws[key] = torch.zeros(n, dtype=torch.uint8, device=device)
+        t = _scratch.of(device).take("gemm", n, torch.uint8, device, zero=True)
     return t
 
 
 def gemm_stream_k_timeouts(device=None) -> int:
     """Sum of the bounded-spin give-ups recorded in this process's GEMM workspaces (diagnostic; expected 0)."""
     tot = 0
-    for (dev, _), t in _gemm_ws.items():
-        if device is None or dev == (device.index if device.index is not None else torch.cuda.current_device()):
-            with torch.cuda.device(dev):
+    for t in _scratch.gemm_buffers():
+        if device is None or t.device.index == (device.index if device.index is not None else torch.cuda.current_device()):
+            with torch.cuda.device(t.device):
                 tot += int(_lib.load().rga3_gemm_stream_k_timeouts(t.data_ptr()))
     return tot
 
@@ -446,16 +419,9 @@ def gemm_tn_many(pairs, out_dtype=torch.bfloat16):
     return outs
 
 
-_tn_cnt = {}
-
-
 def _tn_counters(device):
-    """128 ticket words per (device, stream or workspace_scope) for the fused slab sum of gemm_tn: zeroed once, the kernel leaves them zero."""
-    key = _ws_key(device)
-    t = _tn_cnt.get(key)
-    if t is None:
-        t = _tn_cnt[key] = torch.zeros(256, dtype=torch.int32, device=device)     # [0, 128): gemm_tn tiles; [128, 256): colsum column blocks
-    return t
+    """128 ticket words per Scratch for the fused slab sum of gemm_tn: zeroed once, the kernel leaves them zero."""
+    return _scratch.of(device).take("tn", 256, torch.int32, device, zero=True)     # [0, 128): gemm_tn tiles; [128, 256): colsum column blocks
 
 
 _attn_impl_or = [0]
@@ -847,9 +813,6 @@ def sam_select_objptr(iou, obj, toks, proj, no_obj_ptr):
     return best[0], sel, best[1], ptr
 
 
-_memattn_ws = {}
-
-
 def memattn_cross(q, k, m, scale: float, nsplit: int = 0, partials: bool = False):
     """SAM2 memory cross-attention with the values kept in memory space (csrc/memattn.hip): softmax(scale q k^T) m -> [Nq, 64] bf16.
     q [Nq, 256], k [Nk, 256] bf16 (projected and rotated; row strides free), m [Nk, 64] bf16 the un-projected memory rows.  The caller applies the value
@@ -866,10 +829,7 @@ def memattn_cross(q, k, m, scale: float, nsplit: int = 0, partials: bool = False
     n = int(L.rga3_memattn_cross_ws_floats(Nq, nsplit))
     if n < 0:
         raise _lib.Rga3Error("memattn_cross: bad workspace query")
-    key = _ws_key(q.device)
-    ws = _memattn_ws.get(key)
-    if ws is None or ws.numel() < n:
-        ws = _memattn_ws[key] = torch.empty(n, dtype=torch.float32, device=q.device)
+    ws = _scratch.of(q.device).take("memattn", n, torch.float32, q.device)
     if partials:     # leave the per-slice partial results in the workspace: (sums [nsplit, Nq, 64], (max, sum) [nsplit, Nq, 2], nsplit) for memlayer_rows
         _lib.check(L.rga3_memattn_cross(q.data_ptr(), k.data_ptr(), m.data_ptr(), None, Nq, Nk, q.stride(0), k.stride(0), m.stride(0), 0,
                                         float(scale), int(nsplit), ws.data_ptr(), _stream()), "memattn_cross")
@@ -981,7 +941,6 @@ def mask_jf_counts(annotation, segmentation, void_pixels=None, radius=None):
 # ------------------------------------------------------------------------------------------------ STOM on the device (csrc/stom.hip)
 STOM_MAX_POINTS = 16384
 STOM_MAX_KERNEL = 128
-_stom_ws = {}
 
 
 def _stom_points(name, tracks, visibility, vip_frame_idx):
@@ -1051,10 +1010,7 @@ def stom_mask_composite(frames, overlay, tracks, visibility, vip_frame_idx: int,
     nws = int(L.rga3_stom_ws_bytes(T, H, W))
     if nws < 0:
         raise _lib.Rga3Error("stom_ws_bytes failed: " + _lib.last_error())
-    key = _ws_key(frames.device)
-    ws = _stom_ws.get(key)
-    if ws is None or ws.numel() < nws:
-        ws = _stom_ws[key] = torch.empty(nws, dtype=torch.uint8, device=frames.device)
+    ws = _scratch.of(frames.device).take("stom", nws, torch.uint8, frames.device)
     out = torch.empty_like(frames)
     _lib.check(L.rga3_stom_mask_composite(frames.data_ptr(), overlay.data_ptr(), tracks.data_ptr(), visibility.data_ptr(), out.data_ptr(), ws.data_ptr(), nws, T, H, W, N,
                                           int(vip_frame_idx), spans.ctypes.data, int(ksize), half_widths.ctypes.data, int(radius), _stream()), "stom_mask_composite")
@@ -1165,9 +1121,6 @@ def gemv_w8(a, wq, sw, bias=None, residual=None, act: str = "none", out_dtype=to
     return out
 
 
-_decattn_ws = {}
-
-
 def decode_attn_slice_keys() -> int:
     """Keys per slice of decode_attn (a compile-time constant of csrc/decattn.hip): a sequence with n visible keys is cut into ceil(n / this) slices."""
     return int(_lib.load().rga3_decode_attn_slice_keys())
@@ -1185,7 +1138,7 @@ def decode_attn(qkv, cos, sin, k_cache, v_cache, lens, Hq: int, Hkv: int, scale:
     cos / sin [B, D] f32, k_cache / v_cache [B, cap, Hkv, D] bf16 (any sequence / token / head strides, unit stride on D), lens [B] int32 on the device = tokens
     already stored.  Rotates q and the new k, stores the rotated k row and the v row at position lens[b], returns softmax(scale q K^T) V over rows 0 .. lens[b]
     as [B, Hq, D] bf16.  A sequence with lens[b] >= cap writes nothing and gets NaN rows.  ws: f32 workspace of decode_attn_ws_floats(B, cap, Hq, D) floats (kept per
-    device and stream / workspace_scope when not given)."""
+    Scratch -- scratch.of -- when not given)."""
     if any(t is not None and not t.is_cuda for t in (qkv, cos, sin, k_cache, v_cache, lens, out, ws)):
         raise _lib.Rga3Error("decode_attn: needs device tensors (no CPU fallback on the product path)")
     assert qkv.dtype == k_cache.dtype == v_cache.dtype == torch.bfloat16 and qkv.dim() == 3 and k_cache.dim() == 4 and v_cache.dim() == 4
@@ -1200,11 +1153,7 @@ def decode_attn(qkv, cos, sin, k_cache, v_cache, lens, Hq: int, Hkv: int, scale:
     assert out.dtype == torch.bfloat16 and tuple(out.shape) == (B, Hq, D) and out.stride(2) == 1 and (out.stride(1) == D or Hq == 1)
     L = _lib.load()
     if ws is None:
-        n = decode_attn_ws_floats(B, cap, Hq, D)
-        key = _ws_key(qkv.device)
-        ws = _decattn_ws.get(key)
-        if ws is None or ws.numel() < n:
-            ws = _decattn_ws[key] = torch.empty(n, dtype=torch.float32, device=qkv.device)
+        ws = _scratch.of(qkv.device).take("decattn", decode_attn_ws_floats(B, cap, Hq, D), torch.float32, qkv.device)
     assert ws.dtype == torch.float32 and ws.is_contiguous()
     _lib.check(L.rga3_decode_attn(qkv.data_ptr(), cos.data_ptr(), sin.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), lens.data_ptr(), out.data_ptr(),
                                   ws.data_ptr(), ws.numel(), B, Hq, Hkv, D, cap, qkv.stride(0),
@@ -1468,7 +1417,7 @@ def check_gemm_health(device=None):
     end of bench.py's timed regions and by the training tests."""
     n = gemm_stream_k_timeouts(device)
     if n:
-        for t in _gemm_ws.values():     # recovery: re-arm every flag word so later launches do not read a stale slab
+        for t in _scratch.gemm_buffers():     # recovery: re-arm every flag word so later launches do not read a stale slab
             t[:4096].zero_()
         raise _lib.Rga3Error(f"stream-K GEMM hand-off timed out {n} time(s): results since the last check are not trustworthy (workspace flags re-zeroed)")
 
@@ -1486,8 +1435,8 @@ class GemmHealthWatch:
         if self.n % self.every:
             return
         self.examine()
-        for (dev, _), t in _gemm_ws.items():
-            with torch.cuda.device(dev):
+        for t in _scratch.gemm_buffers():
+            with torch.cuda.device(t.device):
                 off = int(_lib.load().rga3_gemm_timeout_counter_offset())
                 if off < 0:
                     continue
@@ -1502,7 +1451,7 @@ class GemmHealthWatch:
         for host, ev in pend:
             ev.synchronize()      # recorded `every` steps ago: already complete
             if int(host[0]) != 0:
-                for t in _gemm_ws.values():
+                for t in _scratch.gemm_buffers():
                     t[:4096].zero_()
                 raise _lib.Rga3Error(f"stream-K GEMM hand-off timed out {int(host[0])} time(s) in the last {2 * self.every} optimizer steps: their results are not "
                                      "trustworthy (workspace flags re-zeroed)")
@@ -1515,8 +1464,7 @@ def poll_gemm_health():
     """End of evaluate() / generate(): issue a non-blocking fetch of every GEMM workspace's give-up counter and examine the fetch of the PREVIOUS call (no device
     synchronisation).  A stream-K owner that gave up has already poisoned its output tile with +inf (csrc/gemm_bf16.hip), so the product itself is never a finite wrong
     one; this turns the poisoned result into a raised Rga3Error at the next call at the latest."""
-    if _gemm_ws:
-        _inference_watch.poll()
+    _inference_watch.poll()
 
 
 # ------------------------------------------------------------------------------------------------ mask-path backward kernels

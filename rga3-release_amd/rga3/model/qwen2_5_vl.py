@@ -1178,13 +1178,12 @@ class Qwen2_5_VLForConditionalGeneration(nn.Module):
         step over static inputs (token ids [B], positions [3, B], device-side cache lengths).  Returns the replay state; its "logits" are those of the step
         just taken.  The eager step and the captured one write the same cache row, so the cache is consistent whichever ran last.
         One sequence on the varlen route captures over StaticKVCache; set_decode_attention("cache") captures B sequences over StaticBatchKVCache."""
-        dev = tok.device
-        B = tok.shape[0]
+        dev, B = tok.device, tok.shape[0]
         batched = self.decode_attention == "cache"
         n_stored = list(cache.lens)
-        st = {"tok": tok.clone(), "pos3": torch.from_numpy(np.broadcast_to(pos_host[None], (3, B)).copy()).to(dev),
-              "kv": StaticBatchKVCache(cache, dev) if batched else StaticKVCache(cache, dev)}
-        st["cu_q"] = torch.arange(B + 1, dtype=torch.int32, device=dev)   # every tensor the captured launches read must outlive the graph: keep it in st
+        # every tensor the captured launches read must outlive the graph, and the scratch the capture bakes in is dropped with it (ops.workspace_scope): keep them in st
+        st = {"tok": tok.clone(), "pos3": torch.from_numpy(np.broadcast_to(pos_host[None], (3, B)).copy()).to(dev), "scratch": ops.Scratch(),
+              "kv": StaticBatchKVCache(cache, dev) if batched else StaticKVCache(cache, dev), "cu_q": torch.arange(B + 1, dtype=torch.int32, device=dev)}
 
         def body():
             h, _ = self.model(ops.gather_rows(self.model.embed_tokens.weight, st["tok"]), st["pos3"], st["cu_q"], 1, st["kv"])
@@ -1193,17 +1192,11 @@ class Qwen2_5_VLForConditionalGeneration(nn.Module):
             st["kv"].advance()
             return lg
 
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with ops.workspace_scope(("decode-graph", id(st))):     # the scratch the capture bakes in belongs to THIS graph, not to a stream handle (ops.workspace_scope)
-            with torch.cuda.stream(side):
-                body()
-            torch.cuda.current_stream().wait_stream(side)
-            st["pos3"] -= 1                # rewind the state the warm-up advanced; the warm-up wrote cache row n_stored, the capture rewrites it
+        def rewind():                      # the state the warm-up advanced; the warm-up wrote cache row n_stored, the capture rewrites it
+            st["pos3"] -= 1
             st["kv"].reset(n_stored if batched else n_stored[0])
-            st["graph"] = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(st["graph"]):
-                st["logits"] = body()
+
+        st["graph"], st["logits"] = ops.capture_step(body, st["scratch"], between=rewind)
         st["graph"].replay()          # capturing executes nothing: the state still says "this step" -- now run it for real
         cache.lens = n_stored         # the host-side bookkeeping of the eager cache is not used any more during this call
         return st
@@ -1238,12 +1231,7 @@ class Qwen2_5_VLForConditionalGeneration(nn.Module):
             cap = (S + max_new_tokens + 1023) // 1024 * 1024
             # (keyed by the batch size, the attention route and the decode-weight mode as well: a step captured for one of them is never replayed for another)
             dstate = self.__dict__.setdefault("_decode_states", {}).setdefault((cap, str(dev), self.dtype, B, attn_mode, self.decode_weights), {})
-            # the captured launches read the weights (and the packs built from them) through their pointers: any in-place update since the
-            # capture bumps a parameter version and the graph is dropped (re-captured on this call)
-            sig = tuple((p.data_ptr(), p._version) for p in self.parameters())
-            if dstate.get("sig") != sig:
-                dstate.clear()
-                dstate["sig"] = sig
+            ops.drop_if_weights_changed(dstate, self)      # an in-place update since the capture drops the graph: it is re-captured on this call
             if "cache" not in dstate:
                 dstate["cache"] = KVCache(c.num_hidden_layers, B, cap, c.num_key_value_heads, c.head_dim, dev, self.dtype)
             cache = dstate["cache"]
@@ -1270,7 +1258,6 @@ class Qwen2_5_VLForConditionalGeneration(nn.Module):
         deltas = self.rope_deltas.cpu().numpy().reshape(B) if self.rope_deltas is not None else np.zeros(B, dtype=np.int64)
         pos_host = am.detach().cpu().numpy().astype(bool).sum(1).astype(np.int64) - 1 + deltas    # mrope position of the last prefill token (modeling_qwen2_5_vl.py:1160-1172)
         cu_dec = torch.arange(B + 1, dtype=torch.int32, device=dev)
-        dec = None
         # The "everyone has emitted EOS" test is a device -> host sync; taken every step it keeps the host from running ahead of the GPU and
         # exposes every launch.  It is taken every SYNC_EVERY steps instead: a finished batch may run up to SYNC_EVERY - 1 extra steps, whose
         # columns (all pad by construction) are cut below, so the returned ids are exactly those of the step-by-step loop.
@@ -1305,20 +1292,15 @@ class Qwen2_5_VLForConditionalGeneration(nn.Module):
             if graph_ok:
                 # one sequence: the whole step (embedding row, 28 layers, final norm, LM head: ~400 launches of a few microseconds, bound by
                 # launch latency) is captured once (kept on the model per capacity bucket) after a first eager step and replayed per token
-                if dec is None and "graph" in dstate:          # captured by an earlier call: point the static state at this sequence
-                    dec = dstate
-                    dec["pos3"].copy_(torch.from_numpy(np.broadcast_to(pos_host[None], (3, B)).copy()).to(dev))
-                    dec["kv"].reset(cache.lens if attn_mode == "cache" else cache.lens[0])
-                    dec["tok"].copy_(nxt)
-                    dec["graph"].replay()
-                elif dec is None:
-                    dec = self._capture_decode_step(cache, nxt, pos_host)
-                    dstate.update(dec)
-                    dec = dstate
+                if "graph" not in dstate:
+                    dstate.update(self._capture_decode_step(cache, nxt, pos_host))
                 else:
-                    dec["tok"].copy_(nxt)
-                    dec["graph"].replay()
-                logits = dec["logits"]
+                    if step == 0:            # captured by an earlier call: point the static state at this sequence
+                        dstate["pos3"].copy_(torch.from_numpy(np.broadcast_to(pos_host[None], (3, B)).copy()).to(dev))
+                        dstate["kv"].reset(cache.lens if attn_mode == "cache" else cache.lens[0])
+                    dstate["tok"].copy_(nxt)
+                    dstate["graph"].replay()
+                logits = dstate["logits"]
                 continue
             if attn_mode == "cache":      # this route's step holds no host <-> device sync at all: the positions go up from pinned memory
                 pos3 = upload(np.broadcast_to(pos_host[None], (3, B)).copy(), dev)

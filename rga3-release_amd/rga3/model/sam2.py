@@ -1102,22 +1102,17 @@ def _graph_cache(m, session=None):
     The check walks ~900 parameters, so a session does it once (weights do not change inside a session)."""
     cache = m.__dict__.setdefault("_frame_graphs", {})
     if session is None or not getattr(session, "_graphs_checked", False):
-        sig = tuple((p.data_ptr(), p._version) for p in m.parameters())
-        if cache.get("sig") != sig:
-            cache.clear()
-            cache["sig"] = sig
+        ops.drop_if_weights_changed(cache, m)
         if session is not None:
             session._graphs_checked = True
     slot = getattr(session, "slot", 0) if session is not None else 0
     if ("pool", slot) not in cache:
         cache[("pool", slot)] = torch.cuda.graph_pool_handle()       # the graphs of one slot never run concurrently: one private pool per slot
-        # ... and one CAPTURE stream + one scratch scope per slot: ops.py keys its scratch (stream-K slabs / flags, the memory-attention partial sums, the TN
-        # counters) by (device, current stream), and the pointers a capture sees are baked into the graph -- slots whose graphs replay concurrently
-        # (MultiObjectSession) must not share them (ADVICE r5, high).  A capture stream of its own is not enough: torch.cuda.Stream() cycles through a pool of 32,
-        # so some later eager stream IS a slot's capture stream and would share that graph's scratch while the graph replays elsewhere -- warm-up and capture
-        # therefore run inside ops.workspace_scope(("sam2", id(m), slot)): the baked scratch is keyed by the slot, and no eager launch can ever see it.
+        # ... and one CAPTURE stream + one Scratch per slot: the pointers a capture sees (stream-K slabs / flags, the memory-attention partial sums, the TN counters)
+        # are baked into the graph, and slots whose graphs replay concurrently (MultiObjectSession) must not share them (ADVICE r5, high).  A capture stream of its
+        # own is not enough (ops.workspace_scope says why): warm-up and capture run inside the slot's Scratch, which lives in this cache exactly as long as the graphs.
         cache[("stream", slot)] = torch.cuda.Stream()
-        cache[("scope", slot)] = ("sam2-frames", id(m), slot)
+        cache[("scope", slot)] = ops.Scratch()
     return cache
 
 
@@ -1195,15 +1190,7 @@ class VideoSession:
             return o["low_res_masks"], o["obj_ptr"], o["best_iou_inds"]
 
         if fresh:
-            side = cache[("stream", self.slot)]
-            side.wait_stream(torch.cuda.current_stream())
-            with ops.workspace_scope(cache[("scope", self.slot)]):
-                with torch.cuda.stream(side):
-                    body()
-                torch.cuda.current_stream().wait_stream(side)
-                ent["graph"] = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(ent["graph"], pool=cache[("pool", self.slot)], stream=side):
-                    ent["outs"] = body()
+            ent["graph"], ent["outs"] = ops.capture_step(body, cache[("scope", self.slot)], stream=cache[("stream", self.slot)], pool=cache[("pool", self.slot)])
         ent["graph"].replay()
         low, ptr, best = ent["outs"]
         return {"low_res_masks": low.clone(), "obj_ptr": ptr.clone(), "best_iou_inds": best.clone()}
@@ -1332,15 +1319,7 @@ class VideoSession:
         moves += [(G["mem"][p0 + dd * k:p0 + (dd + 1) * k], self.non_cond[t - dd]["obj_ptr"].reshape(-1, m.mem_dim)) for dd in range(1, n_pp + 1)]
         ops.copy_many(moves)
         if fresh:
-            side = cache[("stream", self.slot)]
-            side.wait_stream(torch.cuda.current_stream())
-            with ops.workspace_scope(cache[("scope", self.slot)]):
-                with torch.cuda.stream(side):      # warm-up on the slot's capture stream: tuner picks, THIS slot's workspaces and lazily built tables exist before capture
-                    body()
-                torch.cuda.current_stream().wait_stream(side)
-                ent["graph"] = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(ent["graph"], pool=cache[("pool", self.slot)], stream=side):
-                    ent["outs"] = body()
+            ent["graph"], ent["outs"] = ops.capture_step(body, cache[("scope", self.slot)], stream=cache[("stream", self.slot)], pool=cache[("pool", self.slot)])
         ent["graph"].replay()
         outs = [torch.empty_like(o_) for o_ in ent["outs"]]      # the graph's result buffers are overwritten by the next replay
         ops.copy_many(list(zip(outs, ent["outs"])))

@@ -259,6 +259,10 @@ def test_left_padded_batch_of_three_equals_single_sequences(model, dev):
 
 # ------------------------------------------------------------------------------------------------ 5. captured graphs are kept
 def test_captured_step_is_reused_and_follows_the_weights(dev):
+    import gc
+
+    from rga3.hip import ops, scratch
+
     m = fresh_model(dev, snap=True).set_decode_attention("cache")
     ids, am = _left_padded((21, 33), dev, seed=9)
     gen = lambda: m.generate(input_ids=ids, attention_mask=am, max_new_tokens=20, do_sample=False, eos_token_id=-1)
@@ -273,6 +277,19 @@ def test_captured_step_is_reused_and_follows_the_weights(dev):
         m.model.layers[0].self_attn.o_proj.weight.mul_(1.0)          # an in-place update (same values): the captured step is dropped and captured again
         c = gen()
         assert m.__dict__["_decode_states"][key]["graph"] is not graph and torch.equal(a, c)
+        # every further re-capture drops the scratch of the graph it replaces: no Scratch and no GEMM workspace is left behind (one workspace is what a leak costs)
+        one_workspace = ops.gemm_workspace(dev).numel()              # (bytes: a uint8 tensor)
+        gc.collect()
+        owned, allocated = len(scratch._owned), torch.cuda.memory_allocated()
+        for _ in range(3):
+            m.model.layers[0].self_attn.o_proj.weight.mul_(1.0)
+            c = gen()
+            gc.collect()
+            grown = torch.cuda.memory_allocated() - allocated
+            print(f"re-capture: {len(scratch._owned)} owner-held Scratch (was {owned}), memory_allocated grew by {grown} bytes (one workspace: {one_workspace})")
+            assert len(scratch._owned) == owned
+            assert grown < one_workspace
+            assert torch.equal(a, c)
 
 
 # ------------------------------------------------------------------------------------------------ 6. no sync

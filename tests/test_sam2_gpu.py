@@ -367,7 +367,8 @@ def test_concurrent_replay_of_captured_slot_graphs_is_bit_exact(model, dev):
     # distinct objects really produced distinct masks (the comparison above is not between constants)
     assert not torch.equal(got[0], got[1])
     cache = _graph_cache(model.sam2_model)
-    scopes = {("scope", cache[("scope", o)]) for o in range(n_obj)}
-    assert len(scopes) == n_obj                                        # one scratch scope per slot ...
-    keyed = {k[1] for k in list(ops._gemm_ws) + list(ops._memattn_ws) + list(ops._tn_cnt) if k[1] in scopes}
-    assert len(keyed) >= 2, (keyed, scopes)                            # ... and the graphs' scratch is keyed by it, not by a stream handle
+    owners = [cache[("scope", o)] for o in range(n_obj)]
+    assert all(isinstance(s, ops.Scratch) for s in owners) and len({id(s) for s in owners}) == n_obj     # one scratch owner per slot ...
+    ptrs = [{t.data_ptr() for _, t in s.held()} for s in owners]
+    assert sum(1 for p in ptrs if p) >= 2, ptrs                        # ... which holds the graphs' scratch: it is not a stream's
+    assert all(not (ptrs[i] & ptrs[j]) for i in range(n_obj) for j in range(i)), ptrs     # ... and no two slots share a buffer

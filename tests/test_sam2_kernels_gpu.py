@@ -245,6 +245,33 @@ def test_memattn_cross_low_rank_values(dev, Nq, Nk, nsplit):
     assert torch.equal(out, ops.memattn_cross(q.to(dev), k.to(dev), m.to(dev), 256 ** -0.5, nsplit=nsplit))     # run-to-run identical (fixed summation order)
 
 
+def test_memattn_scratch_grows_under_a_live_graph(dev):
+    """A graph captured in a Scratch scope keeps its partial-sum buffer when a later launch in the same scope needs a larger one (one 64-row query block: one key
+    slice at 64 keys, four at 256): the outgrown buffer stays with the owner, so the allocator cannot hand it to anyone else while the graph may still replay."""
+    from rga3.hip import ops
+
+    g = torch.Generator().manual_seed(5)
+    q, k1, m1, k2, m2 = ((torch.randn(n, w, generator=g)).to(torch.bfloat16).to(dev) for n, w in ((64, 256), (64, 256), (64, 64), (256, 256), (256, 64)))
+    scale = 256 ** -0.5
+    want = ops.memattn_cross(q, k1, m1, scale)
+    s = ops.Scratch()
+    graph, out = ops.capture_step(lambda: ops.memattn_cross(q, k1, m1, scale), s)
+    graph.replay()
+    assert torch.equal(out, want)
+    first = s.memattn
+    assert first.numel() == 1 * 64 * 66 and s.retired == []
+    with ops.workspace_scope(s):
+        _, _, nsplit = ops.memattn_cross(q, k2, m2, scale, partials=True)
+    assert nsplit == 4 and s.memattn is not first and s.memattn.numel() == 4 * 64 * 66          # the scope's buffer grew ...
+    assert any(n == "memattn" and t is first for n, t in s.retired)                             # ... and the first one is still the owner's
+    same_size = [torch.full((first.numel() * 4,), 0xA5, dtype=torch.uint8, device=dev) for _ in range(4)]
+    out.zero_()
+    graph.replay()
+    torch.cuda.synchronize()
+    assert torch.equal(out, want)
+    assert all(bool((t == 0xA5).all()) for t in same_size)
+
+
 def test_fused_decoder_heads_and_selection(dev):
     """csrc/dechead.hip: (a) three-layer MLPs on single token rows, several MLPs x several frames in one launch (mixed output widths, sigmoid on one, outputs written
     into strided views) against fp32 F.linear / relu on the same bf16 weights; (b) argmax over IoU 1..3 (first maximum on ties), plane index, obj_ptr_proj of the chosen
