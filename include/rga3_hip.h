@@ -122,12 +122,18 @@ int rga3_gemm_tn_many(const void* const* ptrs, const int64_t* dims, int n, void*
  *   kernel reads straight out of a fused QKV projection; segments given by cu_q / cu_k (int32, nseg+1).
  *   causal != 0: key j visible to query i iff j <= i + (Lk - Lq) (bottom-right aligned).
  *   lse (optional, f32 [Hq, total_q]) receives log-sum-exp of the scaled scores for the backward pass.
+ *   A query row that sees no key -- causal with Lk < Lq: rows i < Lq - Lk; a segment without keys -- gets o = 0 and lse = -inf, on every kernel
+ *   behind this entry point and behind rga3_attn_varlen_fwd_rope; every row of o (and of lse, when given) of every segment is written.  A segment
+ *   without queries writes nothing.  Keys a row cannot see contribute exactly nothing, but they are still loaded: k and v must be finite
+ *   throughout (0 * Inf is NaN).
+ *   max_k: 0 = unknown, else an upper bound of EVERY segment's key count (cu_k lives on the device and cannot be checked here): with
+ *   0 < max_k <= 256 a non-causal call at D <= 96 runs the whole-segment kernel, whose LDS image is sized from max_k.
  * Replaces flash_attn_varlen_func / F.scaled_dot_product_attention at HF modeling_qwen2_5_vl.py:211-291
  * (ViT windows), :602-700 (causal GQA), reference model/sam2.py:1021 (Hiera), :1476 (two-way decoder),
  * :1543 (memory attention).  D in {16..256}, multiple of 8. impl: 0 = transposed LDS read, 1 = scalar-read
  * variant (debug cross-check). 
  * split_ws (optional, f32, split_ws_elems floats): non-causal calls whose grid would leave most CUs idle (query blocks x heads x
- * segments < 128) over a long key range (max_k >= 1024; max_k is only read for this decision) cut the keys into <= 8 slices, one
+ * segments < 128) over a long key range (max_k >= 1024) cut the keys into <= 8 slices, one
  * workgroup each, and merge them by their log-sum-exp in a second pass; needs nsplit * total_q * Hq * (D + 1) floats.
  * block_q / block_k (0 = off, else powers of two, non-causal): block-diagonal visibility inside a segment -- query i sees key j iff
  * i / block_q == j / block_k -- so that several tiny windows (Hiera's 4- and 16-token windows, model/sam2.py:986-1033) are packed into one
