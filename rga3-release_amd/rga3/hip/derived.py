@@ -40,3 +40,17 @@ def derived(owner, name, *srcs, build, extra=()):
         with torch.no_grad():
             hit = cache[name] = (ver, build()) + tail
     return hit[1]
+
+
+def put(owner, name, srcs, value, extra=()):
+    """Make `value` owner's entry `name` for the sources `srcs`, as derived() would have stored it: for values that are built for many owners at once (one stacked
+    build, every owner given its slice), which derived() then serves until a source or `extra` changes."""
+    owner.__dict__.setdefault("_wt_cache", {})[name] = (versions(*srcs), value) + (() if extra == () else (extra,))
+
+
+def held(owner, name, srcs=None, extra=()):
+    """The value of owner's entry `name`, None if there is none; with `srcs`, None also if derived(owner, name, *srcs, extra=extra) would rebuild it."""
+    hit = owner.__dict__.get("_wt_cache", {}).get(name)
+    if hit is None or (srcs is not None and (hit[0] != versions(*srcs) or hit[2:] != (() if extra == () else (extra,)))):
+        return None
+    return hit[1]

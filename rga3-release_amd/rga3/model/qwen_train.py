@@ -4,9 +4,10 @@ What is trainable on the LLM side of the reference recipe (train_joint.py:193-25
 on q_proj and v_proj of every decoder layer, embed_tokens, lm_head (plus text_hidden_fcs and the SAM2 mask decoder on the mask
 path).  Base projections, norms and the whole ViT are frozen.
 
-Design: ONE autograd node per decoder layer (DecoderLayerFn).  Its forward runs the fused inference kernels under no_grad and
-keeps only the layer input (activation checkpointing == reference's gradient_checkpointing_enable, train_joint.py:188); its
-backward recomputes the layer and back-propagates by hand with the same kernel library: dX GEMMs against cached transposed
+Design: ONE autograd node per decoder layer (DecoderLayerFn).  Its forward runs the layer's kernels under no_grad (_layer_forward)
+and by default keeps the tensors its backward reads (~290 MB per layer at S = 2112); with set_activation_recompute(True) it keeps
+only the layer input (activation checkpointing == reference's gradient_checkpointing_enable, train_joint.py:188) and the backward
+calls _layer_forward again.  The backward back-propagates by hand with the same kernel library: dX GEMMs against cached transposed
 packs of the frozen weights, flash-style attention backward, fused RMSNorm / SwiGLU backward, inverse RoPE, and the small
 LoRA dA/dB products.  The LM head only evaluates the rows that carry a label.
 """
@@ -20,6 +21,7 @@ import torch
 import torch.nn as nn
 
 from ..hip import ops
+from ..hip.derived import held as _held, put as _put
 from ..hip.derived import derived as _wt      # cached derived tensor keyed by the versions of its sources (frozen weights never change -> built once)
 from ..utils.staging import upload
 from . import qwen2_5_vl as _Q
@@ -160,39 +162,41 @@ def _lora_parts(lin):
 # dx += dt_s A  -- the scaling s sits in the SMALL operand of exactly one product per gradient, so no activation-sized tensor is ever rescaled, and the
 # two NN-form products read A^T and (sB)^T.  Round 2 built those per layer and per step with ~14 tiny launches per layer (mul, transpose, float / mul /
 # cast of dB): ~400 launches of a few microseconds in a step.  Here: stack -> one mul / one transposed copy per module family.
-_lora_cache = {}   # id(LoRALinear) -> (key of its parameters, sA [r, in], A^T [in, r], (sB)^T [r, out])
+# Every module OWNS its operands (its "lora" / "lora_cat" entry of rga3.hip.derived, which die with it); lora_refresh only fills those entries for all modules at once.
+def _lora_src(lin):
+    return lin.lora_A["default"].weight, lin.lora_B["default"].weight
 
 
-def _lora_versions(lin):
-    A, B = lin.lora_A["default"].weight, lin.lora_B["default"].weight
-    return A._version, A.data_ptr(), B._version, B.data_ptr()
-
-
-def _lora_build(mods):
-    groups = {}
-    for m in mods:
-        A, B = m.lora_A["default"].weight, m.lora_B["default"].weight
-        groups.setdefault((tuple(A.shape), tuple(B.shape), float(m.scaling), A.dtype, A.device), []).append(m)
+def _lora_stack(mods):
+    """[(sA [r, in], A^T [in, r], (sB)^T [r, out])] of `mods`: one stack, one mul and one transposed copy per family (equal shapes and scaling), not per module."""
+    groups, out = {}, [None] * len(mods)
+    for i, m in enumerate(mods):
+        A, B = _lora_src(m)
+        groups.setdefault((tuple(A.shape), tuple(B.shape), float(m.scaling), A.dtype, A.device), []).append(i)
     with torch.no_grad():
         for (_, _, sc, _, _), grp in groups.items():
-            A = torch.stack([m.lora_A["default"].weight.detach() for m in grp])    # [n, r, in]
-            B = torch.stack([m.lora_B["default"].weight.detach() for m in grp])    # [n, out, r]
+            A = torch.stack([mods[i].lora_A["default"].weight.detach() for i in grp])    # [n, r, in]
+            B = torch.stack([mods[i].lora_B["default"].weight.detach() for i in grp])    # [n, out, r]
             As = A * sc
             At = A.transpose(1, 2).contiguous()
             Bts = (B * sc).transpose(1, 2).contiguous()
-            for i, m in enumerate(grp):
-                _lora_cache[id(m)] = (_lora_versions(m), As[i], At[i], Bts[i])
+            for j, i in enumerate(grp):
+                out[i] = (As[j], At[j], Bts[j])
+    return out
 
 
 def lora_refresh(layers):
-    """Call once per forward: rebuilds the derived operands of every LoRA projection of `layers` if the optimizer has stepped since they were made."""
+    """Call once per forward: rebuilds the derived operands of every LoRA projection of `layers` if the optimizer has stepped since they were made (probed on the
+    first and the last module; a module that is stale on its own is caught by _lora_ops / _lora_cat_ops)."""
     mods = [p for layer in layers for p in (layer.self_attn.q_proj, layer.self_attn.v_proj) if isinstance(p, LoRALinear)]
-    if mods and any((e := _lora_cache.get(id(m))) is None or e[0] != _lora_versions(m) for m in (mods[0], mods[-1])):
-        _lora_build(mods)
+    if mods and any(_held(m, "lora", _lora_src(m), float(m.scaling)) is None for m in (mods[0], mods[-1])):
+        for m, v in zip(mods, _lora_stack(mods)):
+            _put(m, "lora", _lora_src(m), v, float(m.scaling))
     ats = [layer.self_attn for layer in layers if _lora_cat_ok(layer.self_attn)]
-    if ats and len({(a.num_heads, a.num_kv, a.head_dim, a.q_proj.lora_A["default"].weight.shape[0], float(a.q_proj.scaling), float(a.v_proj.scaling)) for a in ats}) == 1:
-        if any((e := _lora_cat.get(id(a))) is None or e[0] != _lora_versions(a.q_proj) + _lora_versions(a.v_proj) for a in (ats[0], ats[-1])):
-            _lora_cat_build(ats)
+    if ats and len({(a.num_heads, a.num_kv, a.head_dim, a.q_proj.lora_A["default"].weight.shape[0]) + _lora_cat_scaling(a) for a in ats}) == 1:
+        if any(_held(a, "lora_cat", _lora_cat_src(a), _lora_cat_scaling(a)) is None for a in (ats[0], ats[-1])):
+            for a, v in zip(ats, _lora_cat_stack(ats)):
+                _put(a, "lora_cat", _lora_cat_src(a), v, _lora_cat_scaling(a))
 
 
 # ---- LoRA's B-side products folded into the frozen q|k|v product and its transpose (rga3_gemm_cat_bf16; VERDICT r3 item 5):
@@ -201,8 +205,6 @@ def lora_refresh(layers):
 # The block matrices of ALL layers are refreshed with the other derived operands, once per optimizer step (zeros stay; only the B blocks are rewritten).
 _LORA_FOLD = os.environ.get("RGA3_LORA_FOLD", "1") != "0"
 _SWIGLU_PRE = os.environ.get("RGA3_SWIGLU_PRE", "1") != "0"     # training forward: SwiGLU inside the gate | up product, pre-activations stored by the same launch
-_lora_cat = {}     # id(attention module) -> (key, W2, Wn)
-_lora_cat_store = {}   # (ids of the module set, Nqkv, r, dtype, device) -> (W2_all, Wn_all)
 
 
 def set_lora_fold(on: bool):
@@ -219,49 +221,57 @@ def _lora_cat_ok(at) -> bool:
     return rq == rv and (2 * rq) % 64 == 0 and q.lora_A["default"].weight.dtype == torch.bfloat16 and q.weight.shape[1] % 64 == 0
 
 
-def _lora_cat_build(ats):
+def _lora_cat_src(at):
+    return at.q_proj.lora_B["default"].weight, at.v_proj.lora_B["default"].weight
+
+
+def _lora_cat_scaling(at):
+    return float(at.q_proj.scaling), float(at.v_proj.scaling)
+
+
+def _rows_of(rows, shape, like):
+    """The tensor of `shape`, dtype and device of `like`, that rows[i] is row i of, for every i; None if there is none."""
+    b = None if any(v is None for v in rows) else rows[0]._base
+    if b is None or tuple(b.shape) != shape or b.dtype != like.dtype or b.device != like.device or not b.is_contiguous():
+        return None
+    st = b.untyped_storage().data_ptr()
+    return b if all(v.untyped_storage().data_ptr() == st and v.storage_offset() == i * b.stride(0) and v.shape == b.shape[1:] and v.is_contiguous()
+                    for i, v in enumerate(rows)) else None
+
+
+def _lora_cat_stack(ats):
+    """[(W2, Wn)] of `ats` (one configuration): rows of two stacked buffers.  The buffers live as long as the modules hold their rows, and are written again when
+    exactly these modules hold all the rows of one pair, in this order (zeros stay, only the B blocks are rewritten: no allocation or memset per step).  Any other
+    set gets buffers of its own, so two layers never share a block matrix (buffers found by shape alone gave every layer of the per-module fallback the
+    same (1, ...) pair, and the backward of all layers but the last read the last layer's (sB)^T)."""
     with torch.no_grad():
         at0 = ats[0]
         Hq, Hk, D = at0.num_heads, at0.num_kv, at0.head_dim
         r = at0.q_proj.lora_A["default"].weight.shape[0]
         Nq, Nall = Hq * D, (Hq + 2 * Hk) * D
+        sq, sv = _lora_cat_scaling(at0)
         Bq = torch.stack([a.q_proj.lora_B["default"].weight.detach() for a in ats])          # [L, Hq D, r]
         Bv = torch.stack([a.v_proj.lora_B["default"].weight.detach() for a in ats])          # [L, Hk D, r]
-        # keyed by the IDENTITY of the module set: keyed by shape alone, the per-module fallback of _lora_cat_ops gave every layer the same (1, ...)
-        # buffer, each build overwriting the previous layer's B blocks -- the backward of all layers but the last then read the last layer's (sB)^T
-        ids = tuple(id(a) for a in ats)
-        key = (ids, Nall, r, Bq.dtype, Bq.device)
-        st = _lora_cat_store.get(key)
-        if st is None:
-            for k in [k for k in _lora_cat_store if k != key and not set(k[0]).isdisjoint(ids)]:    # a module belongs to ONE live set: drop the sets it leaves
-                del _lora_cat_store[k]
-            st = (torch.zeros((len(ats), Nall, 2 * r), dtype=Bq.dtype, device=Bq.device), torch.zeros((len(ats), 2 * r, Nall), dtype=Bq.dtype, device=Bq.device))
-            _lora_cat_store[key] = st
-        W2, Wn = st
+        old = [_held(a, "lora_cat") or (None, None) for a in ats]
+        s2, sn = (len(ats), Nall, 2 * r), (len(ats), 2 * r, Nall)
+        W2, Wn = _rows_of([o[0] for o in old], s2, Bq), _rows_of([o[1] for o in old], sn, Bq)
+        if W2 is None or Wn is None:
+            W2, Wn = Bq.new_zeros(s2), Bq.new_zeros(sn)
         W2[:, :Nq, :r] = Bq
         W2[:, Nq + Hk * D:, r:] = Bv
-        Wn[:, :r, :Nq] = (Bq * float(at0.q_proj.scaling)).transpose(1, 2)
-        Wn[:, r:, Nq + Hk * D:] = (Bv * float(at0.v_proj.scaling)).transpose(1, 2)
-        for i, a in enumerate(ats):
-            _lora_cat[id(a)] = (_lora_versions(a.q_proj) + _lora_versions(a.v_proj), W2[i], Wn[i])
+        Wn[:, :r, :Nq] = (Bq * sq).transpose(1, 2)
+        Wn[:, r:, Nq + Hk * D:] = (Bv * sv).transpose(1, 2)
+        return [(W2[i], Wn[i]) for i in range(len(ats))]
 
 
 def _lora_cat_ops(at):
-    """(W2, Wn) of one attention module, current with its LoRA parameters."""
-    e = _lora_cat.get(id(at))
-    if e is None or e[0] != _lora_versions(at.q_proj) + _lora_versions(at.v_proj):
-        _lora_cat_build([at])
-        e = _lora_cat[id(at)]
-    return e[1], e[2]
+    """(W2, Wn) of one attention module, current with its LoRA parameters (a stale or missing entry is rebuilt for this module alone)."""
+    return _wt(at, "lora_cat", *_lora_cat_src(at), build=lambda: _lora_cat_stack([at])[0], extra=_lora_cat_scaling(at))
 
 
 def _lora_ops(lin):
     """(sA, A^T, (sB)^T) of one projection, current with its parameters (a stale or missing entry is rebuilt for this module alone)."""
-    e = _lora_cache.get(id(lin))
-    if e is None or e[0] != _lora_versions(lin):
-        _lora_build([lin])
-        e = _lora_cache[id(lin)]
-    return e[1], e[2], e[3]
+    return _wt(lin, "lora", *_lora_src(lin), build=lambda: _lora_stack([lin])[0], extra=float(lin.scaling))
 
 
 _drop_state = {"step": 0}
@@ -343,24 +353,6 @@ def qkv_with_lora(at, h1, seeds=None, want_inputs=False):
     return (qkv2, tq, tv, hq, hv) if want_inputs else (qkv2, tq, tv)
 
 
-def _layer_forward_fp8(layer, x, cos, sin, cu, max_len, seeds):
-    """Decoder layer forward with the frozen contractions in e4m3 (same operation order as the recompute in DecoderLayerFn.backward)."""
-    at, mlp = layer.self_attn, layer.mlp
-    Hq, Hk, D = at.num_heads, at.num_kv, at.head_dim
-    T = x.shape[0]
-    w1, w2 = layer.input_layernorm, layer.post_attention_layernorm
-    h1 = ops.rmsnorm(x, w1.weight, w1.variance_epsilon)
-    qkv2 = qkv_with_lora(at, h1, seeds=seeds)[0]
-    qkv = qkv2.view(T, Hq + 2 * Hk, D)
-    ops.rope_(qkv, cos, sin, 0, Hq + Hk)
-    att = ops.attn_varlen(qkv[:, :Hq], qkv[:, Hq:Hq + Hk], qkv[:, Hq + Hk:], cu, cu, max_len, D ** -0.5, causal=True)
-    x1 = _fgemm(att.view(T, Hq * D), at, "wo", (at.o_proj.weight,), lambda: at.o_proj.weight.detach(), residual=x)
-    h2 = ops.rmsnorm(x1, w2.weight, w2.variance_epsilon)
-    wgu, bgu, wd = mlp._packed()
-    gu = _fgemm(h2, mlp, "wgu", (mlp.gate_proj.weight, mlp.up_proj.weight), lambda: wgu, bias=bgu)
-    return _down_from_gu(mlp, gu, wd, x1)
-
-
 def _down_from_gu(mlp, gu, wd, x1):
     """down(silu(gate) * up) + x1 from the interleaved pre-activations.  Under the fp8 switch the SwiGLU kernel emits the e4m3 operand of the down
     projection directly (its bf16 form is never written: 2 x 2 bytes per element less traffic on the widest activation of the layer)."""
@@ -381,9 +373,10 @@ def set_activation_recompute(on: bool):
     _acts["store"] = not on
 
 
-def _layer_forward_store(layer, x, cos, sin, cu, max_len, seeds):
-    """Decoder layer forward for training that returns (y, saved): saved = exactly the tensors DecoderLayerFn.backward otherwise recomputes
-    (same calls in the same order, frozen contractions through _fgemm so the fp8 switch applies)."""
+def _layer_forward(layer, x, cos, sin, cu, max_len, seeds, want_y=True):
+    """The decoder layer's training forward: (y, saved), saved = the tensors DecoderLayerFn.backward reads.  The stored forward, the e4m3 forward that stores
+    nothing, and the backward's recompute (want_y=False: y is None, no down product) are this one function, so they issue the same calls in the same order
+    (frozen contractions through _fgemm so the fp8 switch applies)."""
     at, mlp = layer.self_attn, layer.mlp
     Hq, Hk, D = at.num_heads, at.num_kv, at.head_dim
     T = x.shape[0]
@@ -396,13 +389,13 @@ def _layer_forward_store(layer, x, cos, sin, cu, max_len, seeds):
     x1 = _fgemm(att.view(T, Hq * D), at, "wo", (at.o_proj.weight,), lambda: at.o_proj.weight.detach(), residual=x)
     h2 = ops.rmsnorm(x1, w2.weight, w2.variance_epsilon)
     wgu, bgu, wd = mlp._packed()
-    if not _fp8["on"] and _SWIGLU_PRE and T > 4:
+    if want_y and not _fp8["on"] and _SWIGLU_PRE and T > 4:
         # the gate | up product applies SwiGLU in its epilogue AND leaves the pre-activations the backward needs: no stand-alone SwiGLU launch
         a_, gu = ops.gemm_swiglu_pre(h2, wgu, bgu)
         y = _fgemm(a_, mlp, "wd", (mlp.down_proj.weight,), lambda: wd, bias=mlp.down_proj.bias, residual=x1)
     else:
-        gu = _fgemm(h2, mlp, "wgu", (mlp.gate_proj.weight, mlp.up_proj.weight), lambda: wgu, bias=bgu)
-        y = _down_from_gu(mlp, gu, wd, x1)
+        gu = _fgemm(h2, mlp, "wgu", (mlp.gate_proj.weight, mlp.up_proj.weight), lambda: wgu, bias=bgu)   # pre-activations, interleaved [T, 2*Ip]
+        y = _down_from_gu(mlp, gu, wd, x1) if want_y else None
     return y, (h1, qkv, att, lse, x1, h2, gu, tq, tv, hq_in, hv_in)
 
 
@@ -417,19 +410,15 @@ class DecoderLayerFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, aq, bq, av, bv, layer, cos, sin, cu, max_len, seeds):
         at0 = layer.self_attn
-        ctx.stored = False
-        if _acts["store"]:
+        ctx.stored = _acts["store"]
+        saved = ()
+        if ctx.stored or _fp8["on"]:
             with torch.no_grad():
-                y, saved = _layer_forward_store(layer, x, cos, sin, cu, max_len, seeds)
-            ctx.stored = True
-            ctx.seeds = seeds
-            ctx.layer, ctx.cos, ctx.sin, ctx.cu, ctx.max_len = layer, cos, sin, cu, max_len
-            ctx.save_for_backward(x, *saved)
-            return y
-        if _fp8["on"]:
-            with torch.no_grad():
-                y = _layer_forward_fp8(layer, x, cos, sin, cu, max_len, seeds)
+                y, saved = _layer_forward(layer, x, cos, sin, cu, max_len, seeds)
         else:
+            # bf16 and nothing stored: the INFERENCE route of the layer, not _layer_forward -- at D = 128, max_len >= 256 the rotation happens inside
+            # ops.attn_varlen_rope, and SwiGLU is the gate | up product's epilogue on the plain tilings, so its y differs from _layer_forward's by bf16
+            # roundings (tests/test_train_gpu.py::test_stored_activations_equal_recompute prices that).  Moving it over would change the loss of this mode.
             at0._lora_drop_seeds = seeds          # read by DecoderAttention's native-LoRA path (qwen2_5_vl.py) for this call only
             try:
                 with torch.no_grad():
@@ -438,7 +427,7 @@ class DecoderLayerFn(torch.autograd.Function):
                 at0._lora_drop_seeds = None
         ctx.seeds = seeds
         ctx.layer, ctx.cos, ctx.sin, ctx.cu, ctx.max_len = layer, cos, sin, cu, max_len
-        ctx.save_for_backward(x)
+        ctx.save_for_backward(x, *(saved if ctx.stored else ()))
         return y
 
     @staticmethod
@@ -455,18 +444,9 @@ class DecoderLayerFn(torch.autograd.Function):
             lq, lv = _lora_parts(at.q_proj), _lora_parts(at.v_proj)
             pq, pv = _lora_dropout(at)
             wgu, bgu, wd = mlp._packed()
-            if ctx.stored:
-                h1, qkv, att, lse, x1, h2, gu, tq, tv, hq_in, hv_in = ctx.saved_tensors[1:]
-            else:
-                # ---- recompute forward pieces the backward needs
-                h1 = ops.rmsnorm(x, w1.weight, w1.variance_epsilon)
-                qkv2, tq, tv, hq_in, hv_in = qkv_with_lora(at, h1, seeds=ctx.seeds, want_inputs=True)
-                qkv = qkv2.view(T, Hq + 2 * Hk, D)
-                ops.rope_(qkv, cos, sin, 0, Hq + Hk)
-                att, lse = ops.attn_varlen(qkv[:, :Hq], qkv[:, Hq:Hq + Hk], qkv[:, Hq + Hk:], cu, cu, max_len, D ** -0.5, causal=True, return_lse=True)
-                x1 = _fgemm(att.view(T, Hq * D), at, "wo", (at.o_proj.weight,), lambda: at.o_proj.weight.detach(), residual=x)
-                h2 = ops.rmsnorm(x1, w2.weight, w2.variance_epsilon)
-                gu = _fgemm(h2, mlp, "wgu", (mlp.gate_proj.weight, mlp.up_proj.weight), lambda: wgu, bias=bgu)   # pre-activations, interleaved [T, 2*Ip]
+            # ---- the forward pieces the backward needs: kept, or recomputed
+            h1, qkv, att, lse, x1, h2, gu, tq, tv, hq_in, hv_in = (ctx.saved_tensors[1:] if ctx.stored else
+                                                                   _layer_forward(layer, x, cos, sin, cu, max_len, ctx.seeds, want_y=False)[1])
             q, k, v = qkv[:, :Hq], qkv[:, Hq:Hq + Hk], qkv[:, Hq + Hk:]
             # ---- MLP backward
             da = _fgemm(dy, mlp, "wd_t", (mlp.down_proj.weight,), lambda: ops.transpose(wd))                                   # [T, Ip]

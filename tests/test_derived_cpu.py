@@ -179,3 +179,21 @@ def test_shared_store_never_exceeds_64_entries():
         derived(None, "neg", w, build=lambda: -w)
         assert len(D._shared) <= 64
     assert derived(None, "neg", ws[-1], build=lambda: 1 / 0) is not None      # the newest entry survives a clear
+
+
+def test_put_stores_what_derived_then_serves():
+    m = Owner()
+    v = torch.full((2, 3), 9.0)
+    D.put(m, "doubled", (m.weight, m.bias), v)                      # a value built elsewhere, e.g. this owner's slice of a build over many owners
+    assert m.__dict__["_wt_cache"]["doubled"] == (versions(m.weight, m.bias), v)
+    assert m.doubled() is v and m.calls == 0 and D.held(m, "doubled") is v and D.held(m, "doubled", (m.weight, m.bias)) is v
+    with torch.no_grad():
+        m.weight.add_(1)
+    assert D.held(m, "doubled") is v and D.held(m, "doubled", (m.weight, m.bias)) is None      # kept, but no longer current
+    assert torch.equal(m.doubled(), m.weight.detach() * 2 + 1) and m.calls == 1
+    D.put(m, "doubled", (m.weight, m.bias), v, extra=5)
+    assert m.__dict__["_wt_cache"]["doubled"][2:] == (5,) and list(m.__dict__["_wt_cache"]) == ["doubled"]
+    assert m.doubled(extra=5) is v and m.calls == 1 and D.held(m, "doubled", (m.weight, m.bias), 5) is v
+    assert D.held(m, "doubled", (m.weight, m.bias)) is None and D.held(m, "doubled", (m.weight, m.bias), 6) is None
+    assert m.doubled(extra=6) is not v and m.calls == 2
+    assert D.held(nn.Module(), "doubled") is None

@@ -212,7 +212,7 @@ def test_lora_fold_per_module_fallback_matches_unfolded_route(dev):
 
     assert QT._lora_cat_ok(m.model.layers[0].self_attn)
     l1, g1 = run(True)
-    assert len({QT._lora_cat[id(layer.self_attn)][1].data_ptr() for layer in m.model.layers}) == 3        # one block matrix per layer
+    assert len({QT._lora_cat_ops(layer.self_attn)[0].data_ptr() for layer in m.model.layers}) == 3        # one block matrix per layer
     l0, g0 = run(False)
     assert abs(l1 - l0) <= 5e-3 * abs(l0), (l1, l0)
     errs = {n: rel_l2(g1[n], g0[n]) for n in g0}
@@ -309,10 +309,8 @@ def test_llm_training_step_gradients_with_lora_dropout(dev):
     assert abs(l_eval.item() - ref_eval["loss"].item()) / ref_eval["loss"].item() < 1e-2
 
 
-def test_fp8_frozen_gemm_training_step_close_to_bf16(dev):
-    """Config 5 path: the same LoRA training step with the frozen decoder contractions in e4m3 vs bf16 (dims chosen so every K is a
-    multiple of 128 and the fp8 kernels are the ones that run).  The kernels are pinned against the oracle in test_kernels_gpu.py; here the
-    integration is checked: loss within 2 %, gradients within the e4m3 quantisation noise of the bf16 step, same trainable set."""
+def _fp8_step_model(dev):
+    """(model, ids, am, labels): hidden 256, 2 layers, LoRA r = 8, two sequences of 200 tokens -- every K a multiple of 128, so the fp8 kernels are the ones that run."""
     from rga3.model import qwen_train as QT
     from rga3.model.qwen2_5_vl import Qwen2_5_VLConfig, Qwen2_5_VLForConditionalGeneration
 
@@ -341,6 +339,16 @@ def test_fp8_frozen_gemm_training_step_close_to_bf16(dev):
     labels = ids.clone()
     labels[:, :150] = -100
     am = torch.ones_like(ids)
+    return m, ids, am, labels
+
+
+def test_fp8_frozen_gemm_training_step_close_to_bf16(dev):
+    """Config 5 path: the same LoRA training step with the frozen decoder contractions in e4m3 vs bf16 (dims chosen so every K is a
+    multiple of 128 and the fp8 kernels are the ones that run).  The kernels are pinned against the oracle in test_kernels_gpu.py; here the
+    integration is checked: loss within 2 %, gradients within the e4m3 quantisation noise of the bf16 step, same trainable set."""
+    from rga3.model import qwen_train as QT
+
+    m, ids, am, labels = _fp8_step_model(dev)
 
     def step(fp8):
         QT.set_fp8_frozen_gemms(fp8)
@@ -389,6 +397,38 @@ def test_fp8_frozen_gemm_training_step_close_to_bf16(dev):
     # each e4m3 x e4m3 contraction carries ~5 % relative noise (3 mantissa bits, two operands, random-sign terms do not average it out);
     # eight of them sit on the path from the loss to a LoRA factor
     assert max(errs.values()) < 0.3 and float(np.median(list(errs.values()))) < 0.2, errs
+
+
+def test_fp8_stored_activations_bit_equal_recompute(dev):
+    """With the frozen contractions in e4m3 the forward that stores its activations, the forward that stores nothing and the backward's recompute are ONE function
+    (rga3.model.qwen_train._layer_forward), so a step with stored activations and a step with set_activation_recompute(True) issue the same kernel calls on the same
+    operands: loss and every gradient must be bit-equal.  LoRA dropout 0.1 with the mask counter set back before each step, so both steps draw the same masks; every
+    product of this model is below the GEMM tuner's work threshold, so both steps run the same tilings."""
+    from rga3.model import qwen_train as QT
+
+    m, ids, am, labels = _fp8_step_model(dev)
+    for mod in m.modules():
+        if isinstance(mod, QT.LoRALinear):
+            mod.dropout_p = 0.1
+    step0 = QT._drop_state["step"]
+    res = {}
+    QT.set_fp8_frozen_gemms(True)
+    try:
+        for recompute in (False, True):
+            QT.set_activation_recompute(recompute)
+            QT._drop_state["step"] = step0
+            for p in m.parameters():
+                p.grad = None
+            out = m(input_ids=ids.to(dev), attention_mask=am.to(dev), labels=labels.to(dev))
+            out.loss.backward()
+            res[recompute] = (out.loss.detach().clone(), {n: p.grad.clone() for n, p in m.named_parameters() if p.requires_grad})
+    finally:
+        QT.set_activation_recompute(False)
+        QT.set_fp8_frozen_gemms(False)
+    assert sum("lora_" in n for n in res[True][1]) == 8 and all(bool(g.float().abs().sum() > 0) for g in res[True][1].values())      # every trainable tensor was reached
+    assert torch.equal(res[False][0], res[True][0]), (res[False][0].item(), res[True][0].item())
+    for n in res[True][1]:
+        assert torch.equal(res[False][1][n], res[True][1][n]), n
 
 
 def test_fused_adamw_with_bucket_norm_matches_torch(dev):
